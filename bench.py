@@ -17,10 +17,15 @@ dfmi_synth_snr record: sample i is a function of (seed, i) only). Timing: barrie
 + synchronize on both sides of exactly K steps, MAX over ranks (all_reduce MAX of
 the elapsed time).
 
-Extra JSON fields: roofline (demod kernel, HIP events on the launch stream),
-cpu_baseline (oracle restatement of _fit_parallel with a Pool on the host's
-cores, rank 0 at N=1 only, bounded sample), parity (max |dphi| of the GPU vs that
-oracle on the same sample).
+A plain run sets up, ramps and warms up, times the K steps and prints the headline
+line (metric, value, unit, higher_is_better, dtype, ms_per_step and the workload's
+description). --dump-outputs DIR also writes what the last timed step computed.
+
+--full adds the extra JSON fields, each from runs of its own: roofline (demod kernel,
+HIP events on the launch stream), kernels_ms, window_breakdown, the batch's status
+check, scaling_anchor, extra_configs, cpu_baseline (oracle restatement of
+_fit_parallel with a Pool on the host's cores, rank 0 at N=1 only, bounded sample)
+and parity (max |dphi| of the GPU vs that oracle on the same sample).
 """
 from __future__ import annotations
 
@@ -57,6 +62,14 @@ def parse():
     ap.add_argument("--channels", type=int, default=1,
                     help="records in the batch (config 3: 2 channels, main m=6 and witness m=4.3, each "
                          "seeded by its own buffer 0), segments split evenly; 1 GPU only")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: per-kernel and roofline figures, "
+                         "the window breakdown, the batch's status check, the scaling anchor, the extra configs, "
+                         "the CPU baselines and the parity against the oracle (--no-cpu-baseline, --no-extra and "
+                         "--cpu-* select within it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0's batch) as DIR/<name>.npy: "
+                         "amp, m, phi, psi, dc, ssq (float64) and fitok (float32), one entry per segment")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample", type=int, default=None,
                     help="segments in the CPU-baseline sample (default max(8000, 500 per process))")
@@ -771,10 +784,81 @@ def scaling_anchor(torch, dev, lib, _lib, stream, cfg, steps, warmup):
     return res
 
 
+def kernels_alone(torch, dev, lib, _lib, stream, cfg, x, nall, R, w0, nrep, lm=True):
+    """Side measurements before the steps (HIP events, mean of nrep launches): the standalone
+    row demodulation over the batch (dfmi_demod_rows, no seed: the record pipeline's bulk
+    code, the roofline kernel) and, with lm, the LM kernel alone over component-major QI of
+    every segment. Returns (demodulation ms, LM ms or None, the demodulation kernel's name)."""
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    rows = torch.empty((nall, lib.dfmi_qi_row_stride(NDATA)), dtype=torch.float64, device=dev)
+
+    def demod():
+        rc = lib.dfmi_demod_rows(x.data_ptr(), nall, R, R, NDATA, w0, 0, rows.data_ptr(), _lib.DFMI_MEM_DEVICE,
+                                 stream.cuda_stream)
+        _lib.check(rc, "dfmi_demod_rows")
+
+    for _ in range(5):
+        demod()
+    ev0.record(stream)
+    for _ in range(nrep):
+        demod()
+    ev1.record(stream)
+    ev1.synchronize()
+    rows_ms = ev0.elapsed_time(ev1) / nrep
+    rows_kname = lib.dfmi_last_demod_kernel().decode()
+    if not lm:
+        return rows_ms, None, rows_kname
+    qi = torch.empty((2 * NDATA, nall), dtype=torch.float64, device=dev)
+    dcb = torch.empty(nall, dtype=torch.float64, device=dev)
+    lm_out = torch.empty((4, nall), dtype=torch.float64, device=dev)
+    lm_ssq = torch.empty(nall, dtype=torch.float64, device=dev)
+    lm_st = torch.empty(nall, dtype=torch.int32, device=dev)
+    gdev = torch.tensor([1.0, 6.0, 0.0, 0.0], dtype=torch.float64, device=dev)
+
+    def lm_only():
+        rc = lib.dfmi_lm(qi.data_ptr(), nall, NDATA, gdev.data_ptr(), 0, nall, cfg, lm_out.data_ptr(),
+                         lm_ssq.data_ptr(), lm_st.data_ptr(), _lib.DFMI_MEM_DEVICE, stream.cuda_stream)
+        _lib.check(rc, "dfmi_lm")
+
+    _lib.check(lib.dfmi_demod(x.data_ptr(), nall, R, R, NDATA, w0, 0, qi.data_ptr(), dcb.data_ptr(),
+                              _lib.DFMI_MEM_DEVICE, stream.cuda_stream), "dfmi_demod")
+    lm_only()
+    ev0.record(stream)
+    for _ in range(nrep):
+        lm_only()
+    ev1.record(stream)
+    ev1.synchronize()
+    return rows_ms, ev0.elapsed_time(ev1) / nrep, rows_kname
+
+
+DUMP_COLUMNS = ("amp", "m", "phi", "psi", "dc", "ssq")  # the rows of dfmi_nls_record's out, in order
+DUMP_MAX_SEGMENTS = 1_000_000  # 6 fp64 + the fp32 status + the fp64 index: 60 B per segment, 60 MB
+
+
+def dump_outputs(path, out, ok):
+    """What the timed path returned in its last step (out (6, n) fp64 and ok (n,) int32 on the
+    device), as path/<name>.npy: amp, m, phi, psi, dc, ssq in float64 and fitok in float32.
+    Beyond DUMP_MAX_SEGMENTS segments a fixed sample of them (drawn with SEED, ascending; their
+    positions in segment_index.npy) is written instead, so the files stay under 64 MB."""
+    os.makedirs(path, exist_ok=True)
+    res = out.cpu().numpy()
+    st = ok.cpu().numpy()
+    n = st.shape[0]
+    if n > DUMP_MAX_SEGMENTS:
+        idx = np.sort(np.random.default_rng(SEED).choice(n, DUMP_MAX_SEGMENTS, replace=False))
+        res, st = res[:, idx], st[idx]
+        np.save(os.path.join(path, "segment_index.npy"), idx.astype(np.float64))
+    for c, name in enumerate(DUMP_COLUMNS):
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(res[c], dtype=np.float64))
+    np.save(os.path.join(path, "fitok.npy"), st.astype(np.float32))
+
+
 def main():
     args = parse()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ:
         if args.gpus > 1:  # no torchrun: one rank process per GPU, launched here before any GPU call
             t = args.launch_timeout if args.launch_timeout is not None else launch_timeout(args, args.gpus)
@@ -788,7 +872,7 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
-    want_base = rank == 0 and world == 1 and not args.no_cpu_baseline and not args.demod_only
+    want_base = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.demod_only
     pre = cpu_baseline(args) if want_base else None
     # one process per GPU: bind the device first, so RCCL's barrier / all_reduce run
     # on this rank's GPU
@@ -840,9 +924,6 @@ def main():
     out = torch.empty((6, nrec * nbuf), dtype=torch.float64, device=dev)
     ok = torch.empty(nrec * nbuf, dtype=torch.int32, device=dev)
     nall = nrec * nbuf  # segments in the batch (demodulation / LM-only timings run over all of them)
-    qi = torch.empty((2 * NDATA, nall), dtype=torch.float64, device=dev)
-    dcb = torch.empty(nall, dtype=torch.float64, device=dev)
-    rows = torch.empty((nall, lib.dfmi_qi_row_stride(NDATA)), dtype=torch.float64, device=dev)
     stream = torch.cuda.current_stream()
 
     def step():
@@ -850,82 +931,51 @@ def main():
                                  cfg, out.data_ptr(), ok.data_ptr(), _lib.DFMI_MEM_DEVICE, stream.cuda_stream)
         _lib.check(rc, "dfmi_nls_record")
 
-    def demod():  # the record pipeline's demodulation (row layout): the roofline kernel
-        rc = lib.dfmi_demod_rows(x.data_ptr(), nall, R, R, NDATA, w0, 0, rows.data_ptr(), _lib.DFMI_MEM_DEVICE,
-                                 stream.cuda_stream)
-        _lib.check(rc, "dfmi_demod_rows")
-
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     nrep = max(200, args.steps)
-    # ---- side measurements first (untimed): the standalone row demodulation (dfmi_demod_rows,
-    # no seed: the same bulk code) and the LM kernel alone over component-major QI
-    for _ in range(5):
-        demod()
-    ev0.record(stream)
-    for _ in range(nrep):
-        demod()
-    ev1.record(stream)
-    ev1.synchronize()
-    rows_ms = ev0.elapsed_time(ev1) / nrep
+    if args.full or args.demod_only:  # side measurements first (untimed)
+        rows_ms, lm_ms, rows_kname = kernels_alone(torch, dev, lib, _lib, stream, cfg, x, nall, R, w0, nrep,
+                                                   lm=not args.demod_only)
     if args.demod_only:  # profile helper: nothing but the timed demodulation kernel
         if rank == 0:
-            print(json.dumps({"metric": "demod only (profile helper)", "kernel": lib.dfmi_last_demod_kernel().decode(),
-                              "avg_launch_ms": rows_ms, "roofline": {"kernel": lib.dfmi_last_demod_kernel().decode()}}),
-                  flush=True)
+            print(json.dumps({"metric": "demod only (profile helper)", "kernel": rows_kname,
+                              "avg_launch_ms": rows_ms, "roofline": {"kernel": rows_kname}}), flush=True)
         if world > 1:
             dist.destroy_process_group()
         return
-    lm_out = torch.empty((4, nall), dtype=torch.float64, device=dev)
-    lm_ssq = torch.empty(nall, dtype=torch.float64, device=dev)
-    lm_st = torch.empty(nall, dtype=torch.int32, device=dev)
-    gdev = torch.tensor([1.0, 6.0, 0.0, 0.0], dtype=torch.float64, device=dev)
-
-    def lm_only():
-        rc = lib.dfmi_lm(qi.data_ptr(), nall, NDATA, gdev.data_ptr(), 0, nall, cfg, lm_out.data_ptr(),
-                         lm_ssq.data_ptr(), lm_st.data_ptr(), _lib.DFMI_MEM_DEVICE, stream.cuda_stream)
-        _lib.check(rc, "dfmi_lm")
-
-    _lib.check(lib.dfmi_demod(x.data_ptr(), nall, R, R, NDATA, w0, 0, qi.data_ptr(), dcb.data_ptr(),
-                              _lib.DFMI_MEM_DEVICE, stream.cuda_stream), "dfmi_demod")
-    lm_only()
-    ev0.record(stream)
-    for _ in range(nrep):
-        lm_only()
-    ev1.record(stream)
-    ev1.synchronize()
-    lm_ms = ev0.elapsed_time(ev1) / nrep
-    # ---- roofline of the step's dominant kernel, HIP events on the launch stream, over
-    # whole steps: these untimed steps are also the ramp immediately before the window (the
-    # clocks come up over the first ~35 demodulation-sized launches, 0.58 -> 0.50 ms,
-    # profiles/r02m kernel trace), so a short driver window carries no ramp-up
+    # ---- the ramp: 40 + nrep untimed steps immediately before the window (the clocks come up
+    # over the first ~35 demodulation-sized launches, 0.58 -> 0.50 ms, profiles/r02m kernel
+    # trace), so a short driver window carries no ramp-up
     for _ in range(40):
         step()
-    # nrep >= 200 steps (~0.11 s): the kernel's mean over these dominates any rocprofv3 average
-    # of the same run, ramp launches included (profiles/r03*_frac_check.json); dfmi_step_timing
-    # records events around the fused seed + demodulation launch (the dominant kernel) and
-    # the LM launch of every step, on the step's stream
-    _lib.check(lib.dfmi_step_timing(1), "dfmi_step_timing")
+    if args.full:
+        # roofline of the step's dominant kernel, HIP events on the launch stream, over the
+        # ramp's nrep >= 200 whole steps (~0.11 s): the kernel's mean over these dominates any
+        # rocprofv3 average of the same run, ramp launches included
+        # (profiles/r03*_frac_check.json); dfmi_step_timing records events around the fused
+        # seed + demodulation launch (the dominant kernel) and the LM launch of every step,
+        # on the step's stream
+        _lib.check(lib.dfmi_step_timing(1), "dfmi_step_timing")
     for _ in range(nrep):
         step()
-    _lib.check(lib.dfmi_step_timing(0), "dfmi_step_timing")
-    td, tl, tn = np.zeros(1), np.zeros(1), np.zeros(1, dtype=np.int64)
-    _lib.check(lib.dfmi_step_timing_read(_lib.ptr(td), _lib.ptr(tl), _lib.ptr(tn)), "dfmi_step_timing_read")
-    step_kname = lib.dfmi_last_demod_kernel().decode()
-    if int(tn[0]) != nrep:
-        raise SystemExit(f"step timing: {int(tn[0])} marked steps of {nrep} (pipeline not fused: {step_kname})")
-    demod_ms, lm_step_ms = float(td[0]) / nrep, float(tl[0]) / nrep
-    demod_ms_max = demod_ms
-    per_rank = [{"rank": rank, "step_demod_seed_ms": round(demod_ms, 4), "step_lm_ms": round(lm_step_ms, 4)}]
-    if world > 1:  # the slowest rank's dominant kernel (every rank runs the same shape)
-        tt = torch.tensor([demod_ms], dtype=torch.float64, device=dev)
-        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        demod_ms_max = float(tt.item())
-        # every rank's fused launch carries its own fit of the record's buffer 0 (the seed):
-        # reported per rank, so a rank whose seed fit runs long shows here
-        per_rank = [None] * world
-        dist.all_gather_object(per_rank, {"rank": rank, "step_demod_seed_ms": round(demod_ms, 4),
-                                          "step_lm_ms": round(lm_step_ms, 4)})
-    kname = step_kname
+    if args.full:
+        _lib.check(lib.dfmi_step_timing(0), "dfmi_step_timing")
+        td, tl, tn = np.zeros(1), np.zeros(1), np.zeros(1, dtype=np.int64)
+        _lib.check(lib.dfmi_step_timing_read(_lib.ptr(td), _lib.ptr(tl), _lib.ptr(tn)), "dfmi_step_timing_read")
+        kname = lib.dfmi_last_demod_kernel().decode()
+        if int(tn[0]) != nrep:
+            raise SystemExit(f"step timing: {int(tn[0])} marked steps of {nrep} (pipeline not fused: {kname})")
+        demod_ms, lm_step_ms = float(td[0]) / nrep, float(tl[0]) / nrep
+        demod_ms_max = demod_ms
+        per_rank = [{"rank": rank, "step_demod_seed_ms": round(demod_ms, 4), "step_lm_ms": round(lm_step_ms, 4)}]
+        if world > 1:  # the slowest rank's dominant kernel (every rank runs the same shape)
+            tt = torch.tensor([demod_ms], dtype=torch.float64, device=dev)
+            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+            demod_ms_max = float(tt.item())
+            # every rank's fused launch carries its own fit of the record's buffer 0 (the seed):
+            # reported per rank, so a rank whose seed fit runs long shows here
+            per_rank = [None] * world
+            dist.all_gather_object(per_rank, {"rank": rank, "step_demod_seed_ms": round(demod_ms, 4),
+                                              "step_lm_ms": round(lm_step_ms, 4)})
     fn = step
     # ---- the timed window: W untimed warmup steps, barrier + synchronize, exactly K steps,
     # synchronize + barrier, MAX over ranks. A roctx range "timed_window" brackets it (seen by
@@ -949,43 +999,11 @@ def main():
         tt = torch.tensor([el], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         el = float(tt.item())
-    window_diag = window_breakdown(torch, lib, _lib, fn, stream, args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, ok)
     ms = el / args.steps * 1e3
     total_segments = nseg * world  # units of work; the seed replicas on ranks > 0 are not counted
     value = total_segments * args.steps / el
-    bytes_per_seg = 8 * R + 8 * (2 * NDATA + 1)  # read the segment, write QI + dc
-    achieved = nall * bytes_per_seg / (demod_ms * 1e-3) / 1e9
-    family = kname.split("<")[0]
-    traffic, traffic_src = None, None
-    pmc = os.path.join(ROOT, "profiles", "pmc_demod.json")
-    if os.path.exists(pmc):  # PMC pass of the same kernel and workload (scripts/profile_round.sh)
-        with open(pmc) as f:
-            rec = json.load(f)
-        if family and family in rec.get("kernel", "") and rec.get("algorithmic_bytes_per_launch") == \
-                nall * bytes_per_seg:
-            traffic, traffic_src = rec.get("hbm_bytes_per_launch"), "profiles/pmc_demod.json"
-    # the whole step (seed + demodulation + LM) at SURVEY.md §8(d)'s algorithmic bytes per
-    # segment: 8 R read + 56 B of results (6 fp64 + the status padded to 8 B); the 168-B
-    # demodulation rows are an intermediate of the step, not its output
-    e2e_bytes_per_seg = 8 * R + 56
-    e2e = nall * e2e_bytes_per_seg / (ms * 1e-3) / 1e9
-    roof = {"kernel": kname, "bound": "hbm", "achieved": round(achieved, 1),
-            "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
-            "traffic_source": traffic_src, "avg_launch_ms": round(demod_ms, 4),
-            "timing": f"HIP events around the step's own {kname} launch inside dfmi_nls_record "
-                      f"(dfmi_step_timing), mean over {nrep} steps",
-            "algorithmic_bytes_per_launch": nall * bytes_per_seg,
-            "end_to_end_frac": round(e2e / HBM_PEAK_GBS, 4),
-            "end_to_end_note": "SURVEY.md §8(d) algorithmic bytes of the step (8 R + 56 B per segment) / "
-                               "ms_per_step / peak: the seed and the LM after the demodulation included"}
-    if world > 1:
-        roof["avg_launch_ms_max_over_ranks"] = round(demod_ms_max, 4)
-        roof["frac_min_over_ranks"] = round(nall * bytes_per_seg / (demod_ms_max * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
-
-    # parity on the timed batch itself: status-0 fraction and a sanity check of the estimates
-    st = ok.cpu().numpy()
-    res = out.cpu().numpy()
-
     line = {"metric": METRIC, "value": round(value, 1), "unit": "segments/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 4), "higher_is_better": True,
             "scaling": plan["scaling"], "vs_baseline": None, "dtype": "f64",
@@ -997,22 +1015,52 @@ def main():
                        "parallelism": f"shard{world}"},
             "world": {"size": world, "backend": backend, "ranks": ranks,
                       "launcher": "bench.py self-launch" if os.environ.get("DFMI_SELF_LAUNCHED") else
-                      ("torchrun" if world > 1 else "single process")},
-            "roofline": roof,
-            "kernels_ms": {"step_demod_seed": round(demod_ms, 4), "step_lm": round(lm_step_ms, 4),
-                           "demod_rows_alone": round(rows_ms, 4), "lm_alone_all_segments": round(lm_ms, 4)},
-            "window_breakdown": window_diag,
-            "per_rank_kernels_ms": per_rank,
-            "batch_status0_frac": float(np.mean(st == 0)),
-            "batch_m_mean": float(res[1].mean())}
+                      ("torchrun" if world > 1 else "single process")}}
     if args.tune:
         line["tuning"] = args.tune
-    if world == 1 and nrec == 1 and args.segments is None:
+    if args.full:
+        bytes_per_seg = 8 * R + 8 * (2 * NDATA + 1)  # read the segment, write QI + dc
+        achieved = nall * bytes_per_seg / (demod_ms * 1e-3) / 1e9
+        family = kname.split("<")[0]
+        traffic, traffic_src = None, None
+        pmc = os.path.join(ROOT, "profiles", "pmc_demod.json")
+        if os.path.exists(pmc):  # PMC pass of the same kernel and workload (scripts/profile_round.sh)
+            with open(pmc) as f:
+                rec = json.load(f)
+            if family and family in rec.get("kernel", "") and rec.get("algorithmic_bytes_per_launch") == \
+                    nall * bytes_per_seg:
+                traffic, traffic_src = rec.get("hbm_bytes_per_launch"), "profiles/pmc_demod.json"
+        # the whole step (seed + demodulation + LM) at SURVEY.md §8(d)'s algorithmic bytes per
+        # segment: 8 R read + 56 B of results (6 fp64 + the status padded to 8 B); the 168-B
+        # demodulation rows are an intermediate of the step, not its output
+        e2e_bytes_per_seg = 8 * R + 56
+        e2e = nall * e2e_bytes_per_seg / (ms * 1e-3) / 1e9
+        roof = {"kernel": kname, "bound": "hbm", "achieved": round(achieved, 1),
+                "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
+                "traffic_source": traffic_src, "avg_launch_ms": round(demod_ms, 4),
+                "timing": f"HIP events around the step's own {kname} launch inside dfmi_nls_record "
+                          f"(dfmi_step_timing), mean over {nrep} steps",
+                "algorithmic_bytes_per_launch": nall * bytes_per_seg,
+                "end_to_end_frac": round(e2e / HBM_PEAK_GBS, 4),
+                "end_to_end_note": "SURVEY.md §8(d) algorithmic bytes of the step (8 R + 56 B per segment) / "
+                                   "ms_per_step / peak: the seed and the LM after the demodulation included"}
+        if world > 1:
+            roof["avg_launch_ms_max_over_ranks"] = round(demod_ms_max, 4)
+            roof["frac_min_over_ranks"] = round(nall * bytes_per_seg / (demod_ms_max * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
+        line["roofline"] = roof
+        line["kernels_ms"] = {"step_demod_seed": round(demod_ms, 4), "step_lm": round(lm_step_ms, 4),
+                              "demod_rows_alone": round(rows_ms, 4), "lm_alone_all_segments": round(lm_ms, 4)}
+        line["window_breakdown"] = window_breakdown(torch, lib, _lib, fn, stream, args.steps)
+        line["per_rank_kernels_ms"] = per_rank
+        # parity on the timed batch itself: status-0 fraction and a sanity check of the estimates
+        line["batch_status0_frac"] = float(np.mean(ok.cpu().numpy() == 0))
+        line["batch_m_mean"] = float(out.cpu().numpy()[1].mean())
+    if args.full and world == 1 and nrec == 1 and args.segments is None:
         # the N = 1 point of the driver's 1 -> 8 curve, on the workload rank 0 fits at N = 8
-        del x, out, ok, qi, dcb, rows, lm_out, lm_ssq, lm_st
+        del x, out, ok
         torch.cuda.empty_cache()
         line["scaling_anchor"] = scaling_anchor(torch, dev, lib, _lib, stream, cfg, args.steps, args.warmup)
-    if world == 1 and not args.no_extra and nrec == 1 and args.segments is None:
+    if args.full and world == 1 and not args.no_extra and nrec == 1 and args.segments is None:
         line["extra_configs"] = extra_configs(torch, dev, lib, _lib, stream, cfg, want_base)
     if pre is not None:
         raw, ref, procs, base, base_c = pre

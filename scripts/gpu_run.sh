@@ -6,7 +6,7 @@
 #   tests=FILES_OR_K   pytest -m gpu on the given files (comma-separated), or -k EXPR if no
 #                      entry ends in .py
 #   smoke              __graft_entry__.smoke()
-#   bench[=ARGS]       python bench.py ARGS (comma-separated) > TAG_bench.json
+#   bench[=ARGS]       python bench.py ARGS (comma-separated; --full for every extra key) > TAG_bench.json
 #   py=SCRIPT[,ARGS]   python -u SCRIPT ARGS > TAG_<script name>.jsonl
 #   prof=SCRIPT[,ARGS] rocprofv3 --kernel-trace --stats of python SCRIPT ARGS -> TAG_prof/
 #   pmc=COUNTERS=SCRIPT[,ARGS]  one rocprofv3 --pmc pass (COUNTERS space-free, '+'-joined)

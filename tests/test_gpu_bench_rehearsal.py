@@ -29,7 +29,7 @@ def test_bench_two_ranks_weak_scaling_line(tmp_path):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()), WORLD_SIZE="2",
                DFMI_DIST_BACKEND="gloo", LOCAL_RANK="0")
     cmd = [sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "1",
-           "--segments", "20000", "--no-cpu-baseline"]
+           "--segments", "20000", "--full", "--no-cpu-baseline"]
     procs = []
     for rank in (1, 0):
         out = open(tmp_path / f"r{rank}.out", "w")
@@ -68,7 +68,7 @@ def test_bench_self_launch_two_ranks(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["DFMI_DIST_BACKEND"] = "gloo"
     cmd = [sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "1",
-           "--segments", "20000", "--no-cpu-baseline"]
+           "--segments", "20000", "--full", "--no-cpu-baseline"]
     p = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=240)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [v for v in p.stdout.strip().splitlines() if v.startswith("{")]
