@@ -19,6 +19,8 @@ LIB_PATH = os.path.join(_HERE, "libdfmi.so")
 
 DFMI_MEM_HOST = 0
 DFMI_MEM_DEVICE = 1
+DFMI_F64 = 0  # sample types of the *_typed entry points
+DFMI_F32 = 1
 MAX_LAMBDA = 16
 
 SYMBOLS = ("dfmi_lm_config_default", "dfmi_demod", "dfmi_lm", "dfmi_nls_record", "dfmi_ekf",
@@ -28,7 +30,7 @@ SYMBOLS = ("dfmi_lm_config_default", "dfmi_demod", "dfmi_lm", "dfmi_nls_record",
            "dfmi_fit_txt_write", "dfmi_py_repr", "dfmi_txt_last_error", "dfmi_wdfmi_fit", "dfmi_ekf_fit",
            "dfmi_record_moments", "dfmi_synth_asd", "dfmi_synth_snr", "dfmi_bessel_eval",
            "dfmi_release_workspaces", "dfmi_step_timing", "dfmi_step_timing_read", "dfmi_ekf_pit_passes",
-           "dfmi_ekf_pit_trace")
+           "dfmi_ekf_pit_trace", "dfmi_demod_typed", "dfmi_demod_rows_typed", "dfmi_nls_record_typed")
 
 
 class DFMIError(RuntimeError):
@@ -202,6 +204,11 @@ def load():
         lib.dfmi_nls_record.argtypes = [P, i64, i64, i64, i32, i32, dbl, i32, P, i32, i64,
                                         ctypes.POINTER(LMConfig), P, P, i32, P]
         lib.dfmi_nls_record.restype = ctypes.c_int
+        # the typed variants: (x, xtype, ...the untyped arguments after x)
+        lib.dfmi_demod_typed.argtypes = [P, i32] + lib.dfmi_demod.argtypes[1:]
+        lib.dfmi_demod_typed.restype = ctypes.c_int
+        lib.dfmi_nls_record_typed.argtypes = [P, i32] + lib.dfmi_nls_record.argtypes[1:]
+        lib.dfmi_nls_record_typed.restype = ctypes.c_int
         lib.dfmi_ekf.argtypes = [P, i64, i64, i64, P, P, P, P, dbl, dbl, i32, i64, P, i32, P]
         lib.dfmi_ekf.restype = ctypes.c_int
         lib.dfmi_ekf_fit.argtypes = [P, i64, i64, i64, P, P, P, P, dbl, dbl, i32, i64, P, i32, P]
@@ -236,6 +243,8 @@ def load():
         lib.dfmi_qi_row_dc.restype = ctypes.c_int32
         lib.dfmi_demod_rows.argtypes = [P, i64, i64, i32, i32, dbl, i32, P, i32, P]
         lib.dfmi_demod_rows.restype = ctypes.c_int
+        lib.dfmi_demod_rows_typed.argtypes = [P, i32] + lib.dfmi_demod_rows.argtypes[1:]
+        lib.dfmi_demod_rows_typed.restype = ctypes.c_int
         cp = ctypes.c_char_p
         lib.dfmi_txt_parse_header.argtypes = [cp, i32, P]
         lib.dfmi_txt_parse_header.restype = ctypes.c_int

@@ -95,9 +95,12 @@ class DeepFitFramework:
         for k, v in h.items():
             setattr(self, k, v)
 
-    def load_raw(self, raw_file=None, labels=None, device=None):
+    def load_raw(self, raw_file=None, labels=None, device=None, dtype=None):
         """core.py:259-286: one DeepRawObject per channel (column). With `device`
-        the samples go straight to that GPU (pinned staging) as the raw's data."""
+        the samples go straight to that GPU (pinned staging) as the raw's data; with
+        dtype="float32" as well they stay there as float32 (parsed as float64, cast once;
+        the NLS fitter reads float32 natively). Without `device` the data is the reference's
+        float64 DataFrame and a dtype is refused."""
         from . import textio
         from .data import DeepRawObject
         if raw_file is not None:
@@ -110,7 +113,7 @@ class DeepFitFramework:
             labels = [self.raw_file + "_ch" + str(c) for c in range(self.channr)]
         else:
             assert len(labels) == self.channr
-        _, chans = textio.read_raw(self.raw_file, device=device)
+        _, chans = textio.read_raw(self.raw_file, device=device, dtype=dtype)
         for c in range(self.channr):
             if device is None:
                 import pandas as pd

@@ -21,6 +21,11 @@
 // the 4 waves of the workgroup. The 2·ndata lane-partial sums are reduced with
 // a reduce-scatter butterfly over the 64 lanes (16 values → 17 shuffles per
 // block of 8 harmonics, instead of 16×6).
+//
+// Sample type: the kernels that read samples are templates over XT (SampleT below), double
+// or float; the loads widen in registers and nothing after the load depends on XT. The bin,
+// many-harmonic and seed kernels exist for both; demod_fold_kernel and demod_direct_kernel
+// read doubles only (the host widens another type into a workspace for them).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -110,6 +115,68 @@ struct VecT<2> {
     o[1] = v.y;
   }
 };
+
+// Sample-load trait: how the sample-reading device code fetches a record's samples of type
+// XT. Every load returns doubles; a narrower type is widened in registers right after the
+// load (float -> double is exact), so everything downstream of the load — the phase bins,
+// fold_finish, the QI layouts — is the same code for every XT, and a record of XT samples
+// gives the bits the double kernels give on the widened record as long as the bins still
+// receive their samples in ascending t (the lane mapping below is the double one: lane l
+// holds samples 2l, 2l+1 of a 128-sample chunk, an 8-byte load per lane for float).
+// XT = double is the VecT code above, unchanged. Further sample types (integers) are
+// further specialisations.
+template <typename XT>
+struct SampleT;
+template <>
+struct SampleT<double> {
+  __device__ static __forceinline__ double at(const double* p) { return *p; }
+  template <int VEC>
+  __device__ static __forceinline__ void load(const double* p, double (&o)[VEC]) {
+    VecT<VEC>::load(p, o);
+  }
+  template <int VEC>
+  __device__ static __forceinline__ void load_nt(const double* p, double (&o)[VEC]) {
+    VecT<VEC>::load_nt(p, o);
+  }
+};
+template <>
+struct SampleT<float> {
+  __device__ static __forceinline__ double at(const float* p) { return (double)*p; }
+  template <int VEC>
+  __device__ static __forceinline__ void load(const float* p, double (&o)[VEC]) {
+    if constexpr (VEC == 1) {
+      o[0] = (double)*p;
+    } else {
+      const float2 v = *reinterpret_cast<const float2*>(p);  // global_load_dwordx2
+      o[0] = (double)v.x;
+      o[1] = (double)v.y;
+    }
+  }
+  template <int VEC>
+  __device__ static __forceinline__ void load_nt(const float* p, double (&o)[VEC]) {
+    if constexpr (VEC == 1) {
+      o[0] = (double)__builtin_nontemporal_load(p);
+    } else {
+      typedef float f2v __attribute__((ext_vector_type(2)));
+      const f2v v = __builtin_nontemporal_load(reinterpret_cast<const f2v*>(p));
+      o[0] = (double)v.x;
+      o[1] = (double)v.y;
+    }
+  }
+};
+
+// Widen a record of XT samples into doubles (the typed entry points' fallback for the
+// branches that read doubles only: demod_fold_kernel, demod_direct_kernel): row s of n
+// samples at x + s·sx to y + s·sy.
+template <typename XT>
+__global__ __launch_bounds__(256) void widen_rows_kernel(const XT* __restrict__ x, int64_t nrow, int64_t sx, int64_t n,
+                                                         double* __restrict__ y, int64_t sy) {
+  const int64_t total = nrow * n;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t s = i / n, t = i - s * n;
+    y[s * sy + t] = SampleT<XT>::at(x + s * sx + t);
+  }
+}
 
 // Write one block of HB harmonics (2·HB sums, after butterfly<2·HB>) of segment s.
 template <int HB>
@@ -244,8 +311,8 @@ __device__ __forceinline__ void fold_finish(const double (&y)[MAXSLOT][VEC], con
 // T: basis table (LDS or global), col: the segment's column in qi / dc.
 // MAXSLOT: compile-time bound on nslot = ceil(L / (64·VEC)); LOADS: vector loads
 // kept in flight per lane in the fold loop; NT: non-temporal (streaming) loads.
-template <int VEC, int MAXSLOT, int LOADS = 8, bool NT = true>
-__device__ __forceinline__ void fold_segment(const double* __restrict__ xs, int R, int L, int ndata,
+template <int VEC, int MAXSLOT, int LOADS = 8, bool NT = true, typename XT = double>
+__device__ __forceinline__ void fold_segment(const XT* __restrict__ xs, int R, int L, int ndata,
                                              const double* __restrict__ T, int lane, double* __restrict__ qi,
                                              int64_t qi_ld, int64_t col, double* __restrict__ dc) {
   const int nslot = (L + 64 * VEC - 1) / (64 * VEC);
@@ -274,8 +341,8 @@ __device__ __forceinline__ void fold_segment(const double* __restrict__ xs, int 
 #pragma unroll
       for (int j = 0; j < MAXSLOT; ++j) {
         if (pval[j]) {
-          if constexpr (NT) VecT<VEC>::load_nt(xs + (int64_t)(k + u) * L + pbase[j], v[u][j]);
-          else VecT<VEC>::load(xs + (int64_t)(k + u) * L + pbase[j], v[u][j]);
+          if constexpr (NT) SampleT<XT>::template load_nt<VEC>(xs + (int64_t)(k + u) * L + pbase[j], v[u][j]);
+          else SampleT<XT>::template load<VEC>(xs + (int64_t)(k + u) * L + pbase[j], v[u][j]);
         }
         else {
 #pragma unroll
@@ -294,19 +361,19 @@ __device__ __forceinline__ void fold_segment(const double* __restrict__ xs, int 
     for (int j = 0; j < MAXSLOT; ++j) {
       if (pval[j]) {
         double v[VEC];
-        VecT<VEC>::load(xs + (int64_t)k * L + pbase[j], v);
+        SampleT<XT>::template load<VEC>(xs + (int64_t)k * L + pbase[j], v);
 #pragma unroll
         for (int e = 0; e < VEC; ++e) y[j][e] += v[e];
       }
     }
   }
   if (rem) {  // ragged last cycle: element-wise bounds
-    const double* xr = xs + (int64_t)ncyc * L;
+    const XT* xr = xs + (int64_t)ncyc * L;
 #pragma unroll
     for (int j = 0; j < MAXSLOT; ++j)
 #pragma unroll
       for (int e = 0; e < VEC; ++e)
-        if (pval[j] && pbase[j] + e < rem) y[j][e] += xr[pbase[j] + e];
+        if (pval[j] && pbase[j] + e < rem) y[j][e] += SampleT<XT>::at(xr + (pbase[j] + e));
   }
 
   fold_finish<VEC, MAXSLOT>(y, pval, pbase, R, L, ndata, T, lane, qi, qi_ld, col, dc);
@@ -384,13 +451,13 @@ __global__ __launch_bounds__(kBlockThreads) void demod_fold_kernel(
 // the next segment's first PFN chunks (at `next`, if not null) are issued into pf
 // before this segment's contraction, so the wave has loads in flight while it
 // contracts.
-template <int MAXSLOT, int LOADS, bool NT, int HB, bool ROWS, int PFN = 0, bool ROW_LDS = false>
-__device__ __forceinline__ void bins_segment(const double* __restrict__ xs0, int R, int L, int ndata,
+template <int MAXSLOT, int LOADS, bool NT, int HB, bool ROWS, int PFN = 0, bool ROW_LDS = false, typename XT = double>
+__device__ __forceinline__ void bins_segment(const XT* __restrict__ xs0, int R, int L, int ndata,
                                              const double* __restrict__ T, double* __restrict__ ybin, int lane,
                                              const bool (&pval)[MAXSLOT], const int (&pbase)[MAXSLOT],
                                              double* __restrict__ qi, int64_t qi_ld, int64_t col,
                                              double* __restrict__ dc, double (*pf)[2] = nullptr,
-                                             const double* __restrict__ next = nullptr) {
+                                             const XT* __restrict__ next = nullptr) {
   typedef double d2v __attribute__((ext_vector_type(2)));
   const int nch = R >> 7;           // full 128-sample chunks
   const int tail = R - (nch << 7);  // samples of the last, partial chunk
@@ -406,7 +473,7 @@ __device__ __forceinline__ void bins_segment(const double* __restrict__ xs0, int
 #pragma unroll
   for (int j = 0; j < MAXSLOT; ++j)
     if (pval[j]) *reinterpret_cast<d2v*>(ybin + pbase[j]) = d2v{0.0, 0.0};
-  const double* __restrict__ xs = xs0 + 2 * lane;
+  const XT* __restrict__ xs = xs0 + 2 * lane;
   int p0 = 0;  // bin of the chunk's first sample: (128 c) mod L
   int c = 0;
   if constexpr (PFN > 0) {
@@ -422,8 +489,8 @@ __device__ __forceinline__ void bins_segment(const double* __restrict__ xs0, int
     double v[LOADS][2];
 #pragma unroll
     for (int u = 0; u < LOADS; ++u) {
-      if constexpr (NT) VecT<2>::load_nt(xs + (c + u) * 128, v[u]);
-      else VecT<2>::load(xs + (c + u) * 128, v[u]);
+      if constexpr (NT) SampleT<XT>::template load_nt<2>(xs + (c + u) * 128, v[u]);
+      else SampleT<XT>::template load<2>(xs + (c + u) * 128, v[u]);
     }
 #pragma unroll
     for (int u = 0; u < LOADS; ++u) {
@@ -441,14 +508,14 @@ __device__ __forceinline__ void bins_segment(const double* __restrict__ xs0, int
 #pragma unroll
     for (int u = 0; u < LOADS; ++u) {
       if (u < rem) {
-        if constexpr (NT) VecT<2>::load_nt(xs + (c + u) * 128, v[u]);
-        else VecT<2>::load(xs + (c + u) * 128, v[u]);
+        if constexpr (NT) SampleT<XT>::template load_nt<2>(xs + (c + u) * 128, v[u]);
+        else SampleT<XT>::template load<2>(xs + (c + u) * 128, v[u]);
       }
     }
     const int t0 = 2 * lane;
     double tv0 = 0.0, tv1 = 0.0;
-    if (t0 < tail) tv0 = xs[nch * 128];  // partial chunk: element-wise (R may be odd)
-    if (t0 + 1 < tail) tv1 = xs[nch * 128 + 1];
+    if (t0 < tail) tv0 = SampleT<XT>::at(xs + nch * 128);  // partial chunk: element-wise (R may be odd)
+    if (t0 + 1 < tail) tv1 = SampleT<XT>::at(xs + (nch * 128 + 1));
 #pragma unroll
     for (int u = 0; u < LOADS; ++u) {
       if (u < rem) {
@@ -466,11 +533,11 @@ __device__ __forceinline__ void bins_segment(const double* __restrict__ xs0, int
   }
   if constexpr (PFN > 0) {
     if (next) {
-      const double* __restrict__ xn = next + 2 * lane;
+      const XT* __restrict__ xn = next + 2 * lane;
 #pragma unroll
       for (int u = 0; u < PFN; ++u) {
-        if constexpr (NT) VecT<2>::load_nt(xn + u * 128, pf[u]);
-        else VecT<2>::load(xn + u * 128, pf[u]);
+        if constexpr (NT) SampleT<XT>::template load_nt<2>(xn + u * 128, pf[u]);
+        else SampleT<XT>::template load<2>(xn + u * 128, pf[u]);
       }
     }
   }
@@ -496,9 +563,9 @@ __device__ __forceinline__ void bins_segment(const double* __restrict__ xs0, int
 // probe (diagnostics, may be null): s_memrealtime at the entry of workgroups 0 and
 // gridDim-1 and at the exit of workgroup 0's wave 0 ([3], [4], [5]).
 constexpr int kProbeWaves = 16384;  // per-wave slots of the diagnostics probe buffer
-template <int MAXSLOT, int LOADS, bool ROWS, int PFN = 0>
+template <int MAXSLOT, int LOADS, bool ROWS, int PFN = 0, typename XT = double>
 __device__ __forceinline__ void bins_kernel_body(
-    const double* __restrict__ x, int64_t nseg, int64_t seg_stride, int R, int L, int ndata,
+    const XT* __restrict__ x, int64_t nseg, int64_t seg_stride, int R, int L, int ndata,
     const double* __restrict__ tab, double* __restrict__ qi, int64_t qi_ld, double* __restrict__ dc,
     uint64_t* __restrict__ probe, int block0 = 0) {
   // block0: leading workgroups that play another role (the fused seed kernel, seed.h)
@@ -529,18 +596,18 @@ __device__ __forceinline__ void bins_kernel_body(
     // software pipeline across this wave's segments (see bins_segment PFN)
     double pf[PFN > 0 ? PFN : 1][2];
     if (s0 < nseg) {
-      const double* __restrict__ x0 = x + s0 * seg_stride + 2 * lane;
+      const XT* __restrict__ x0 = x + s0 * seg_stride + 2 * lane;
 #pragma unroll
-      for (int u = 0; u < PFN; ++u) VecT<2>::load_nt(x0 + u * 128, pf[u]);
+      for (int u = 0; u < PFN; ++u) SampleT<XT>::template load_nt<2>(x0 + u * 128, pf[u]);
     }
     for (int64_t s = s0; s < nseg; s += ds)
-      bins_segment<MAXSLOT, LOADS, true, kHarmBlock, ROWS, PFN>(x + s * seg_stride, R, L, ndata, lds_dyn, ybin, lane,
-                                                                pval, pbase, qi, qi_ld, s, dc, pf,
-                                                                s + ds < nseg ? x + (s + ds) * seg_stride : nullptr);
+      bins_segment<MAXSLOT, LOADS, true, kHarmBlock, ROWS, PFN, false, XT>(
+          x + s * seg_stride, R, L, ndata, lds_dyn, ybin, lane, pval, pbase, qi, qi_ld, s, dc, pf,
+          s + ds < nseg ? x + (s + ds) * seg_stride : nullptr);
   } else {
     for (int64_t s = s0; s < nseg; s += ds)
-      bins_segment<MAXSLOT, LOADS, true, kHarmBlock, ROWS>(x + s * seg_stride, R, L, ndata, lds_dyn, ybin, lane, pval,
-                                                           pbase, qi, qi_ld, s, dc);
+      bins_segment<MAXSLOT, LOADS, true, kHarmBlock, ROWS, 0, false, XT>(x + s * seg_stride, R, L, ndata, lds_dyn, ybin,
+                                                                         lane, pval, pbase, qi, qi_ld, s, dc);
   }
   if (probe && threadIdx.x == 0 && bid == 0) probe[5] = __builtin_amdgcn_s_memrealtime();
   // per-wave exit times (probe[16 + global wave], up to kProbeWaves waves) and the
@@ -556,12 +623,12 @@ __device__ __forceinline__ void bins_kernel_body(
   }
 }
 
-template <int MAXSLOT, int LOADS, bool ROWS, int PFN = 0>
+template <int MAXSLOT, int LOADS, bool ROWS, int PFN = 0, typename XT = double>
 __global__ __launch_bounds__(kBlockThreads) void demod_bins_kernel(
-    const double* __restrict__ x, int64_t nseg, int64_t seg_stride, int R, int L, int ndata,
+    const XT* __restrict__ x, int64_t nseg, int64_t seg_stride, int R, int L, int ndata,
     const double* __restrict__ tab, double* __restrict__ qi, int64_t qi_ld, double* __restrict__ dc,
     uint64_t* __restrict__ probe) {
-  bins_kernel_body<MAXSLOT, LOADS, ROWS, PFN>(x, nseg, seg_stride, R, L, ndata, tab, qi, qi_ld, dc, probe);
+  bins_kernel_body<MAXSLOT, LOADS, ROWS, PFN, XT>(x, nseg, seg_stride, R, L, ndata, tab, qi, qi_ld, dc, probe);
 }
 
 // Many harmonics (the bin kernel's LDS basis, 2·ndata·L doubles, no longer fits beside the
@@ -594,9 +661,9 @@ __host__ __device__ constexpr int wide_set(int L, int NO, int KSEG) {
   // (even: the sets' pair loads / stores stay 16-B aligned)
   return (((L + 4 > (64 * NO * (KSEG + 1) + KSEG - 1) / KSEG) ? L + 4 : (64 * NO * (KSEG + 1) + KSEG - 1) / KSEG) + 1) & ~1;
 }
-template <int LOADS, int PFN>
-__device__ __forceinline__ void wide_fold(const double* __restrict__ xs0, int R, int L, double* ybin, int lane,
-                                          double (*pf)[2], const double* __restrict__ next) {
+template <int LOADS, int PFN, typename XT = double>
+__device__ __forceinline__ void wide_fold(const XT* __restrict__ xs0, int R, int L, double* ybin, int lane,
+                                          double (*pf)[2], const XT* __restrict__ next) {
   typedef double d2v __attribute__((ext_vector_type(2)));
   const int nch = R >> 7;
   const int tail = R - (nch << 7);
@@ -612,7 +679,7 @@ __device__ __forceinline__ void wide_fold(const double* __restrict__ xs0, int R,
 #pragma unroll
   for (int j = 0; j < 2; ++j)
     if (2 * (lane + 64 * j) < L) *reinterpret_cast<d2v*>(ybin + 2 * (lane + 64 * j)) = d2v{0.0, 0.0};
-  const double* __restrict__ xs = xs0 + 2 * lane;
+  const XT* __restrict__ xs = xs0 + 2 * lane;
   int p0 = 0;
   int c = 0;
   if constexpr (PFN > 0) {
@@ -627,7 +694,7 @@ __device__ __forceinline__ void wide_fold(const double* __restrict__ xs0, int R,
   for (; c + LOADS <= nch; c += LOADS) {
     double v[LOADS][2];
 #pragma unroll
-    for (int u = 0; u < LOADS; ++u) VecT<2>::load_nt(xs + (c + u) * 128, v[u]);
+    for (int u = 0; u < LOADS; ++u) SampleT<XT>::template load_nt<2>(xs + (c + u) * 128, v[u]);
 #pragma unroll
     for (int u = 0; u < LOADS; ++u) {
       add_chunk(p0, v[u]);
@@ -640,11 +707,11 @@ __device__ __forceinline__ void wide_fold(const double* __restrict__ xs0, int R,
     double v[LOADS][2];
 #pragma unroll
     for (int u = 0; u < LOADS; ++u)
-      if (u < rem) VecT<2>::load_nt(xs + (c + u) * 128, v[u]);
+      if (u < rem) SampleT<XT>::template load_nt<2>(xs + (c + u) * 128, v[u]);
     const int t0 = 2 * lane;
     double tv0 = 0.0, tv1 = 0.0;
-    if (t0 < tail) tv0 = xs[nch * 128];
-    if (t0 + 1 < tail) tv1 = xs[nch * 128 + 1];
+    if (t0 < tail) tv0 = SampleT<XT>::at(xs + nch * 128);
+    if (t0 + 1 < tail) tv1 = SampleT<XT>::at(xs + (nch * 128 + 1));
 #pragma unroll
     for (int u = 0; u < LOADS; ++u) {
       if (u < rem) {
@@ -662,9 +729,9 @@ __device__ __forceinline__ void wide_fold(const double* __restrict__ xs0, int R,
   }
   if constexpr (PFN > 0) {
     if (next) {
-      const double* __restrict__ xn = next + 2 * lane;
+      const XT* __restrict__ xn = next + 2 * lane;
 #pragma unroll
-      for (int u = 0; u < PFN; ++u) VecT<2>::load_nt(xn + u * 128, pf[u]);
+      for (int u = 0; u < PFN; ++u) SampleT<XT>::template load_nt<2>(xn + u * 128, pf[u]);
     }
   }
 }
@@ -674,8 +741,8 @@ __device__ __forceinline__ void wide_fold(const double* __restrict__ xs0, int R,
 // short segment, R = 200, is otherwise one exposed memory round trip of 1.6 KB: 0.1 of peak,
 // r05ad). Lane l's two samples of a chunk sit in one segment (R even), at position t, bin p;
 // (k, t, p) advance by 128 samples a chunk (p -= R mod L at each segment wrap).
-template <int LOADS>
-__device__ __forceinline__ void wide_fold_flat(const double* __restrict__ xg, int nk, int R, int L, double* ybase,
+template <int LOADS, typename XT = double>
+__device__ __forceinline__ void wide_fold_flat(const XT* __restrict__ xg, int nk, int R, int L, double* ybase,
                                                int ws, int lane) {
   typedef double d2v __attribute__((ext_vector_type(2)));
   for (int k = 0; k < nk; ++k)
@@ -687,11 +754,11 @@ __device__ __forceinline__ void wide_fold_flat(const double* __restrict__ xg, in
   const int tail = (int)(total - (nch << 7));
   const int rL = R % L;
   int k = (2 * lane) / R, t = 2 * lane - k * R, p = t % L;
-  auto add = [&](const d2v v) {
+  auto add = [&](const double (&v)[2]) {
     d2v* yp = reinterpret_cast<d2v*>(ybase + k * ws + p);
     d2v y = *yp;
-    y.x += v.x;
-    y.y += v.y;
+    y.x += v[0];
+    y.y += v[1];
     *yp = y;
     t += 128;
     p += 128;
@@ -703,23 +770,23 @@ __device__ __forceinline__ void wide_fold_flat(const double* __restrict__ xg, in
       if (p < 0) p += L;
     }
   };
-  const d2v* __restrict__ xv = reinterpret_cast<const d2v*>(xg) + lane;
+  const XT* __restrict__ xv = xg + 2 * lane;  // the lane's sample pair of chunk 0
   int64_t c = 0;
   for (; c + LOADS <= nch; c += LOADS) {
-    d2v v[LOADS];
+    double v[LOADS][2];
 #pragma unroll
-    for (int u = 0; u < LOADS; ++u) v[u] = __builtin_nontemporal_load(xv + (c + u) * 64);
+    for (int u = 0; u < LOADS; ++u) SampleT<XT>::template load_nt<2>(xv + (c + u) * 128, v[u]);
 #pragma unroll
     for (int u = 0; u < LOADS; ++u) add(v[u]);
   }
   {
     const int rem = (int)(nch - c);
-    d2v v[LOADS];
+    double v[LOADS][2];
 #pragma unroll
     for (int u = 0; u < LOADS; ++u)
-      if (u < rem) v[u] = __builtin_nontemporal_load(xv + (c + u) * 64);
-    d2v tv = d2v{0.0, 0.0};
-    if (2 * lane < tail) tv = xv[nch * 64];  // partial last chunk (tail even: both samples or none)
+      if (u < rem) SampleT<XT>::template load_nt<2>(xv + (c + u) * 128, v[u]);
+    double tv[2] = {0.0, 0.0};
+    if (2 * lane < tail) SampleT<XT>::template load<2>(xv + nch * 128, tv);  // partial last chunk (tail even: both samples or none)
 #pragma unroll
     for (int u = 0; u < LOADS; ++u)
       if (u < rem) add(v[u]);
@@ -729,9 +796,9 @@ __device__ __forceinline__ void wide_fold_flat(const double* __restrict__ xg, in
 
 // HALF (NO = 1, 2·ndata + 1 <= 32): the two half-waves contract different segments (lanes
 // 0..31 the even k, 32..63 the odd), halving the contraction's instructions per segment.
-template <int NO, int KSEG, int LOADS, int PFN, int HALF = 0, int TD = (NO >= 4 ? 2 : 8 / NO)>
+template <int NO, int KSEG, int LOADS, int PFN, int HALF = 0, int TD = (NO >= 4 ? 2 : 8 / NO), typename XT = double>
 __global__ __launch_bounds__(kBlockThreads, 3) void demod_wide_kernel(  // 3 waves per SIMD: <= 168 VGPRs
-    const double* __restrict__ x, int64_t nseg, int64_t seg_stride, int R, int L, int ndata,
+    const XT* __restrict__ x, int64_t nseg, int64_t seg_stride, int R, int L, int ndata,
     const double* __restrict__ tabT, double* __restrict__ qi, int64_t qi_ld, double* __restrict__ dc, int dbg) {
   // dbg (diagnostics, demod_wide_dbg): bit 0 skips the contraction (acc = one bin), bit 1
   // the stores (kept alive by a never-true NaN test) — fold / contraction / store split;
@@ -753,21 +820,21 @@ __global__ __launch_bounds__(kBlockThreads, 3) void demod_wide_kernel(  // 3 wav
   const bool pfok = PFN > 0 && (R >> 7) >= PFN;
   double pf[PFN > 0 ? PFN : 1][2];
   if (pfok && nk > 0 && !(seg_stride == R && !(dbg & 4))) {
-    const double* __restrict__ x0 = x + sbeg * seg_stride + 2 * lane;
+    const XT* __restrict__ x0 = x + sbeg * seg_stride + 2 * lane;
 #pragma unroll
-    for (int u = 0; u < (PFN > 0 ? PFN : 1); ++u) VecT<2>::load_nt(x0 + u * 128, pf[u]);
+    for (int u = 0; u < (PFN > 0 ? PFN : 1); ++u) SampleT<XT>::template load_nt<2>(x0 + u * 128, pf[u]);
   }
   const bool flat = seg_stride == R && !(dbg & 4);  // contiguous segments: one flat stream per wave
-  if (flat && nk > 0) wide_fold_flat<LOADS>(x + sbeg * seg_stride, nk, R, L, ybase, ws, lane);
+  if (flat && nk > 0) wide_fold_flat<LOADS, XT>(x + sbeg * seg_stride, nk, R, L, ybase, ws, lane);
   for (int k = 0; k < nk; ++k) {
     const int64_t s = sbeg + k;
     double* yb = ybase + k * ws;
-    const double* nx = s + 1 < send ? x + (s + 1) * seg_stride : nullptr;
+    const XT* nx = s + 1 < send ? x + (s + 1) * seg_stride : nullptr;
     if (flat) {
     } else if (pfok) {
-      wide_fold<LOADS, PFN>(x + s * seg_stride, R, L, yb, lane, pf, nx);
+      wide_fold<LOADS, PFN, XT>(x + s * seg_stride, R, L, yb, lane, pf, nx);
     } else {
-      wide_fold<LOADS, 0>(x + s * seg_stride, R, L, yb, lane, pf, nullptr);
+      wide_fold<LOADS, 0, XT>(x + s * seg_stride, R, L, yb, lane, pf, nullptr);
     }
     // pair the bins in place: y+ at [0, 2 npp), y- at [ym, ym + 2 npp) (ym even: 16-B aligned
     // pair reads), zero past half; every lane reads all its inputs before any lane writes
@@ -871,13 +938,14 @@ __global__ __launch_bounds__(kBlockThreads, 3) void demod_wide_kernel(  // 3 wav
 // half-period pairing and the lanes-over-outputs contraction of demod_wide_kernel, the same
 // operations in the same order — the segment's QI and dc are bit-identical to what the bulk
 // demod_wide_kernel gives it; written component-major to qi[o * qi_ld + col] / dc[col].
-__device__ __forceinline__ void wide_seed_segment(const double* __restrict__ xs, int R, int L, int ndata,
+template <typename XT = double>
+__device__ __forceinline__ void wide_seed_segment(const XT* __restrict__ xs, int R, int L, int ndata,
                                                   const double* __restrict__ tabT, int no, double* ybin, int lane,
                                                   double* __restrict__ qi, int64_t qi_ld, int64_t col,
                                                   double* __restrict__ dc) {
   typedef double d2v __attribute__((ext_vector_type(2)));
   double pf[1][2];
-  wide_fold<10, 0>(xs, R, L, ybin, lane, pf, nullptr);
+  wide_fold<10, 0, XT>(xs, R, L, ybin, lane, pf, nullptr);
   const int half = L >> 1;
   const int npair = (half + 2) >> 1;
   const int ym = (half + 2) & ~1;
@@ -918,12 +986,13 @@ __device__ __forceinline__ void wide_seed_segment(const double* __restrict__ xs,
 // Fallback when no short integer period exists: per-sample angles
 // fl(fl(h·w0)·t) exactly as fit.py:55-64 forms them, sincos on the device.
 // VALU-bound; only used for unusual f_samp/f_mod ratios.
-__device__ __forceinline__ void direct_segment(const double* __restrict__ xs, int R, int ndata, double w0, int lane,
+template <typename XT = double>
+__device__ __forceinline__ void direct_segment(const XT* __restrict__ xs, int R, int ndata, double w0, int lane,
                                                double* __restrict__ qi, int64_t qi_ld, int64_t col,
                                                double* __restrict__ dc) {
   const int nblk = (ndata + kHarmBlock - 1) / kHarmBlock;
   double tot = 0.0;
-  for (int t = lane; t < R; t += 64) tot += xs[t];
+  for (int t = lane; t < R; t += 64) tot += SampleT<XT>::at(xs + t);
   tot = wave_sum(tot);
   if (lane == 0) dc[col] = tot / (double)R;
   for (int hb = 0; hb < nblk; ++hb) {
@@ -934,7 +1003,7 @@ __device__ __forceinline__ void direct_segment(const double* __restrict__ xs, in
 #pragma unroll
     for (int h = 0; h < kHarmBlock; ++h) wh[h] = (double)(hb * kHarmBlock + h + 1) * w0;
     for (int t = lane; t < R; t += 64) {
-      const double xv = xs[t];
+      const double xv = SampleT<XT>::at(xs + t);
       const double tt = (double)t;
 #pragma unroll
       for (int h = 0; h < kHarmBlock; ++h) {

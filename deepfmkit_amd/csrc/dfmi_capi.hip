@@ -15,6 +15,7 @@
 #include <mutex>
 #include <string>
 #include <tuple>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/dfmi.h"
@@ -490,6 +491,14 @@ constexpr int kMaxSlotCap = 8;
 
 thread_local std::string g_last_demod;  // kernel variant of the last demodulation launch (dfmi_last_demod_kernel)
 
+// Sample types of the typed entry points (dfmi_*_typed): the demodulation and seed launches
+// below are templates over XT; XT = double is the untyped entry points' code. xt_tag: what
+// dfmi_last_demod_kernel appends for a kernel that read XT samples itself.
+template <typename XT>
+const char* xt_tag() {
+  return std::is_same<XT, float>::value ? " [f32]" : "";
+}
+
 // hipOccupancyMaxActiveBlocksPerMultiprocessor, cached per (kernel, LDS bytes): the
 // query costs host time on every call otherwise.
 template <typename K>
@@ -580,11 +589,11 @@ int launch_fold_ms(int ms, const double* x, int64_t nseg, int64_t stride, int R,
 // segment's first 4 chunks are prefetched during the contraction (+1.4 % on the step,
 // profiles/r01g_ab_prefetch.jsonl; 6 chunks tied, 16 loads per group -1.7 %, a rolling
 // pipeline -0.7 %, the contraction interleaved with the next segment's loads level).
-template <int MS, bool ROWS>
-int launch_bins_t(const double* x, int64_t nseg, int64_t stride, int R, int L, int ndata, const double* tab,
+template <int MS, bool ROWS, typename XT>
+int launch_bins_t(const XT* x, int64_t nseg, int64_t stride, int R, int L, int ndata, const double* tab,
                   double* qi, int64_t qi_ld, double* dc, hipStream_t st, int n_cu, size_t lds) {
   constexpr int PFN = MS == 2 ? DFMI_BINS_PFN : 0;
-  auto kern = dfmi::demod_bins_kernel<MS, DFMI_BINS_LOADS, ROWS, PFN>;
+  auto kern = dfmi::demod_bins_kernel<MS, DFMI_BINS_LOADS, ROWS, PFN, XT>;
   lds += DFMI_BINS_LDS_PAD;
   int per_cu = 0;
   if (int orc = occupancy(kern, dfmi::kBlockThreads, lds, &per_cu)) return orc;
@@ -595,7 +604,7 @@ int launch_bins_t(const double* x, int64_t nseg, int64_t stride, int R, int L, i
   HIPCHK(hipGetLastError());
   g_last_demod = std::string("demod_bins_kernel<") + std::to_string(MS) + "," + std::to_string(DFMI_BINS_LOADS) +
                  (ROWS ? ",rows" : "") + "," + std::to_string(PFN) + ">" +
-                 (PFN && (R >> 7) >= PFN ? " (prefetch " + std::to_string(PFN) + ")" : "");
+                 (PFN && (R >> 7) >= PFN ? " (prefetch " + std::to_string(PFN) + ")" : "") + xt_tag<XT>();
   return DFMI_OK;
 }
 
@@ -631,13 +640,14 @@ bool wide_geometry(bool vec2, int L, int ndata) {
   return vec2 && !(L & 1) && L >= 128 && L <= 256 && 2 * ndata + 1 <= 64 * 4 && wide_kseg(L, ndata) > 0;
 }
 
-template <int NO, int KSEG>
-int launch_wide_t(const double* x, int64_t nseg, int64_t stride, int R, int L, int ndata, const double* tabT,
+template <int NO, int KSEG, typename XT>
+int launch_wide_t(const XT* x, int64_t nseg, int64_t stride, int R, int L, int ndata, const double* tabT,
                   double* qi, int64_t qi_ld, double* dc, hipStream_t st, int n_cu) {
   // half-wave contraction where the outputs fit 32 lanes (2·ndata + 1 <= 32)
   const bool half = NO == 1 && 2 * ndata + 1 <= 32 && t_tune.demod_wide_half;
-  auto kern = half ? dfmi::demod_wide_kernel<NO, KSEG, DFMI_WIDE_LOADS, 4, (NO == 1 && KSEG % 2 == 0) ? 1 : 0>
-                   : dfmi::demod_wide_kernel<NO, KSEG, DFMI_WIDE_LOADS, 4, 0>;
+  constexpr int TD = NO >= 4 ? 2 : 8 / NO;  // the kernel's default basis pairs in flight
+  auto kern = half ? dfmi::demod_wide_kernel<NO, KSEG, DFMI_WIDE_LOADS, 4, (NO == 1 && KSEG % 2 == 0) ? 1 : 0, TD, XT>
+                   : dfmi::demod_wide_kernel<NO, KSEG, DFMI_WIDE_LOADS, 4, 0, TD, XT>;
   const size_t lds = (size_t)dfmi::kWavesPerBlock * KSEG * dfmi::wide_set(L, NO, KSEG) * sizeof(double);
   (void)n_cu;
   const int64_t per_block = (int64_t)dfmi::kWavesPerBlock * KSEG;
@@ -646,11 +656,12 @@ int launch_wide_t(const double* x, int64_t nseg, int64_t stride, int R, int L, i
                      tabT, qi, qi_ld, dc, t_tune.demod_wide_dbg);
   HIPCHK(hipGetLastError());
   g_last_demod = "demod_wide_kernel<" + std::to_string(NO) + "," + std::to_string(KSEG) + "," +
-                 std::to_string(DFMI_WIDE_LOADS) + ",4," + (half && KSEG % 2 == 0 ? "1" : "0") + ">";
+                 std::to_string(DFMI_WIDE_LOADS) + ",4," + (half && KSEG % 2 == 0 ? "1" : "0") + ">" + xt_tag<XT>();
   return DFMI_OK;
 }
 
-int launch_wide(int dev, const double* x, int64_t nseg, int64_t stride, int R, int L, int ndata, double w0,
+template <typename XT>
+int launch_wide(int dev, const XT* x, int64_t nseg, int64_t stride, int R, int L, int ndata, double w0,
                 double* qi, int64_t qi_ld, double* dc, hipStream_t st, int n_cu) {
   const int no = wide_no(ndata);
   const double* tabT = nullptr;
@@ -684,7 +695,8 @@ bool bins_applicable(bool vec2, int L, int ndata, size_t lds_cap) {
 }
 
 // Returns 1 if the bin kernel does not apply.
-int try_bins(const double* x, int64_t nseg, int64_t stride, int R, int L, int ndata, const double* tab, double* qi,
+template <typename XT>
+int try_bins(const XT* x, int64_t nseg, int64_t stride, int R, int L, int ndata, const double* tab, double* qi,
              int64_t qi_ld, double* dc, hipStream_t st, int n_cu, bool vec2, size_t lds_cap, bool rows) {
   if (!bins_applicable(vec2, L, ndata, lds_cap)) return 1;
   const size_t lds = ((size_t)2 * ndata * L + (size_t)dfmi::kWavesPerBlock * L) * sizeof(double);
@@ -699,13 +711,37 @@ int try_bins(const double* x, int64_t nseg, int64_t stride, int R, int L, int nd
   return launch_bins_t<8, false>(x, nseg, stride, R, L, ndata, tab, qi, qi_ld, dc, st, n_cu, lds);
 }
 
-bool vec2_ok(const double* x, int64_t stride, int L) {
-  return (L % 2 == 0) && (stride % 2 == 0) && (((uintptr_t)x & 15) == 0);
+// Sample pairs loadable as one vector: rows aligned to two samples (16 B for double, 8 B for
+// float) at an even stride, and an even period.
+template <typename XT>
+bool vec2_ok(const XT* x, int64_t stride, int L) {
+  return (L % 2 == 0) && (stride % 2 == 0) && (((uintptr_t)x & (2 * sizeof(XT) - 1)) == 0);
+}
+
+// The typed entry points' fallback for the branches that read doubles only (the fold and
+// direct kernels): nseg rows of R samples widened into the "x_widen" workspace (even row
+// stride, 16-B aligned), followed by the double branch on it; dfmi_last_demod_kernel then
+// ends in " [f32 widened]".
+template <typename XT>
+int widen_rows(int dev, const XT* x, int64_t nseg, int64_t stride, int R, hipStream_t st, const double** out,
+               int64_t* out_stride) {
+  const int64_t ws = (int64_t)R + (R & 1);
+  void* w = nullptr;
+  if (int rc = workspace(dev, "x_widen", (size_t)nseg * ws * sizeof(double), &w)) return rc;
+  int64_t grid = (nseg * (int64_t)R + 255) / 256;
+  if (grid > (int64_t)t_ds->n_cu * 16) grid = (int64_t)t_ds->n_cu * 16;
+  hipLaunchKernelGGL(dfmi::widen_rows_kernel<XT>, dim3((unsigned)grid), dim3(256), 0, st, x, nseg, stride, (int64_t)R,
+                     (double*)w, ws);
+  HIPCHK(hipGetLastError());
+  *out = (const double*)w;
+  *out_stride = ws;
+  return DFMI_OK;
 }
 
 // Whether demod_device can write the row layout (dfmi_qi_row_stride) for this
 // input: only the bin-in-LDS kernel implements it.
-bool rows_supported(int dev, const double* x, int64_t stride, int R, int ndata, double w0, int period) {
+template <typename XT>
+bool rows_supported(int dev, const XT* x, int64_t stride, int R, int ndata, double w0, int period) {
   int L = period;
   if (L == 0) L = detect_period_impl(w0, R, ndata);
   if (L <= 0) return false;
@@ -715,7 +751,8 @@ bool rows_supported(int dev, const double* x, int64_t stride, int R, int ndata, 
 // Device-pointer demodulation (all pointers on the current device).
 // rows = true: write the row layout (qi + s·qi_ld, dfmi_qi_row_stride; dc inside
 // the row, `dc` unused) — callers check rows_supported() first.
-int demod_device(int dev, const double* x, int64_t nseg, int64_t stride, int R, int ndata, double w0, int period,
+template <typename XT>
+int demod_device(int dev, const XT* x, int64_t nseg, int64_t stride, int R, int ndata, double w0, int period,
                  double* qi, int64_t qi_ld, double* dc, hipStream_t st, bool rows = false) {
   if (nseg == 0) return DFMI_OK;
   int L = period;
@@ -741,23 +778,36 @@ int demod_device(int dev, const double* x, int64_t nseg, int64_t stride, int R, 
       if (rows) return fail(DFMI_ERR_UNSUPPORTED, "row layout needs the bin-in-LDS demodulation kernel");
       if (t_tune.demod_wide && t_tune.demod_kernel == 1 && wide_geometry(vec2, L, ndata))
         return launch_wide(dev, x, nseg, stride, R, L, ndata, w0, qi, qi_ld, dc, st, n_cu);
+      // the fold kernel reads doubles: another sample type is widened first, and the branch
+      // (VEC from the rows' own pair alignment) is the one a double record of this layout takes
+      const double* xd = nullptr;
+      int64_t sd = stride;
+      if constexpr (std::is_same<XT, double>::value) xd = x;
+      else if ((rc = widen_rows(dev, x, nseg, stride, R, st, &xd, &sd))) return rc;
       if (vec2) {
-        return use_lds ? launch_fold_ms<2, true>(ms, x, nseg, stride, R, L, ndata, tab, qi, qi_ld, dc, st, n_cu)
-                       : launch_fold_ms<2, false>(ms, x, nseg, stride, R, L, ndata, tab, qi, qi_ld, dc, st, n_cu);
+        rc = use_lds ? launch_fold_ms<2, true>(ms, xd, nseg, sd, R, L, ndata, tab, qi, qi_ld, dc, st, n_cu)
+                     : launch_fold_ms<2, false>(ms, xd, nseg, sd, R, L, ndata, tab, qi, qi_ld, dc, st, n_cu);
+      } else {
+        rc = use_lds ? launch_fold_ms<1, true>(ms, xd, nseg, sd, R, L, ndata, tab, qi, qi_ld, dc, st, n_cu)
+                     : launch_fold_ms<1, false>(ms, xd, nseg, sd, R, L, ndata, tab, qi, qi_ld, dc, st, n_cu);
       }
-      return use_lds ? launch_fold_ms<1, true>(ms, x, nseg, stride, R, L, ndata, tab, qi, qi_ld, dc, st, n_cu)
-                     : launch_fold_ms<1, false>(ms, x, nseg, stride, R, L, ndata, tab, qi, qi_ld, dc, st, n_cu);
+      if (rc == DFMI_OK && !std::is_same<XT, double>::value) g_last_demod += " [f32 widened]";
+      return rc;
     }
   }
   if (rows) return fail(DFMI_ERR_UNSUPPORTED, "row layout needs the bin-in-LDS demodulation kernel");
+  const double* xd = nullptr;
+  int64_t sd = stride;
+  if constexpr (std::is_same<XT, double>::value) xd = x;
+  else if (int rc = widen_rows(dev, x, nseg, stride, R, st, &xd, &sd)) return rc;
   // direct kernel
   int64_t need = (nseg + dfmi::kWavesPerBlock - 1) / dfmi::kWavesPerBlock;
   int64_t grid = (int64_t)n_cu * 8;
   if (grid > need) grid = need;
-  hipLaunchKernelGGL(dfmi::demod_direct_kernel, dim3((unsigned)grid), dim3(dfmi::kBlockThreads), 0, st, x, nseg,
-                     stride, R, ndata, w0, qi, qi_ld, dc);
+  hipLaunchKernelGGL(dfmi::demod_direct_kernel, dim3((unsigned)grid), dim3(dfmi::kBlockThreads), 0, st, xd, nseg,
+                     sd, R, ndata, w0, qi, qi_ld, dc);
   HIPCHK(hipGetLastError());
-  g_last_demod = "demod_direct_kernel";
+  g_last_demod = std::is_same<XT, double>::value ? "demod_direct_kernel" : "demod_direct_kernel [f32 widened]";
   return DFMI_OK;
 }
 
@@ -889,14 +939,15 @@ int lm_device(int dev, const double* qi, int64_t qi_ld, int ndata, int64_t nrec,
 // Whole record pipeline on device pointers (fitters.py:370-428).
 // Fused seed + bulk demodulation (seed.h demod_seed_bins_kernel) on one stream.
 // Returns 1 when it does not apply (caller uses the two-kernel path).
-int fused_seed_demod(int dev, const double* x, int64_t nrec, int64_t nbuf, int R, int ndata, int L,
+template <typename XT>
+int fused_seed_demod(int dev, const XT* x, int64_t nrec, int64_t nbuf, int R, int ndata, int L,
                      const double* tab, double* rows, int64_t qs, const double* gdev, const dfmi::GuessInline& ginl,
                      const double* jtab, const dfmi::LMConst& c, double* out, int64_t out_ld, int32_t* fitok,
                      hipStream_t st) {
   if (ndata > 16 || L <= 0) return 1;
   const int nslot = (L + 127) / 128;
   if (nslot > 8) return 1;
-  using K = void (*)(const double*, int64_t, int64_t, int64_t, int, int, int, const double*, double*, int64_t,
+  using K = void (*)(const XT*, int64_t, int64_t, int64_t, int, int, int, const double*, double*, int64_t,
                      const double*, dfmi::GuessInline, int, const double*, dfmi::LMConst, double*, int64_t, int64_t,
                      int32_t*, uint64_t*);
   const bool pf = nslot <= 2 && ndata <= 12;  // bins_segment's prefetch (bulk path, MS 2)
@@ -904,12 +955,13 @@ int fused_seed_demod(int dev, const double* x, int64_t nrec, int64_t nbuf, int R
   const size_t lds = ((size_t)2 * ndata * L + (size_t)dfmi::kWavesPerBlock * L) * sizeof(double) +
                      (nslot <= 2 && ndata <= 12 ? DFMI_BINS_LDS_PAD : 0);
   if (ndata <= 12)
-    kern = nslot <= 2 ? dfmi::demod_seed_bins_kernel<2, 12, DFMI_BINS_PFN, DFMI_BINS_LOADS>
-           : nslot <= 4 ? dfmi::demod_seed_bins_kernel<4, 12>
-                                                                          : dfmi::demod_seed_bins_kernel<8, 12>;
+    kern = nslot <= 2   ? dfmi::demod_seed_bins_kernel<2, 12, DFMI_BINS_PFN, DFMI_BINS_LOADS, XT>
+           : nslot <= 4 ? dfmi::demod_seed_bins_kernel<4, 12, 0, 8, XT>
+                        : dfmi::demod_seed_bins_kernel<8, 12, 0, 8, XT>;
   else
-    kern = nslot <= 2 ? dfmi::demod_seed_bins_kernel<2, 16> : nslot <= 4 ? dfmi::demod_seed_bins_kernel<4, 16>
-                                                                       : dfmi::demod_seed_bins_kernel<8, 16>;
+    kern = nslot <= 2   ? dfmi::demod_seed_bins_kernel<2, 16, 0, 8, XT>
+           : nslot <= 4 ? dfmi::demod_seed_bins_kernel<4, 16, 0, 8, XT>
+                        : dfmi::demod_seed_bins_kernel<8, 16, 0, 8, XT>;
   int per_cu = 0;
   if (int orc = occupancy(kern, dfmi::kBlockThreads, lds, &per_cu)) return orc;
   if (per_cu < 1) per_cu = 1;
@@ -933,7 +985,8 @@ int fused_seed_demod(int dev, const double* x, int64_t nrec, int64_t nbuf, int R
   g_last_demod = "demod_seed_bins_kernel<" + std::to_string(nslot <= 2 ? 2 : nslot <= 4 ? 4 : 8) + "," +
                  std::to_string(ndata <= 12 ? 12 : 16) + "," + std::to_string(geo ? DFMI_BINS_PFN : 0) + "," +
                  std::to_string(geo ? DFMI_BINS_LOADS : 8) + ">" +
-                 (pf && (R >> 7) >= DFMI_BINS_PFN ? " (prefetch " + std::to_string(DFMI_BINS_PFN) + ")" : "");
+                 (pf && (R >> 7) >= DFMI_BINS_PFN ? " (prefetch " + std::to_string(DFMI_BINS_PFN) + ")" : "") +
+                 xt_tag<XT>();
   return DFMI_OK;
 }
 
@@ -942,7 +995,8 @@ int fused_seed_demod(int dev, const double* x, int64_t nrec, int64_t nbuf, int R
 // the bulk demodulation on the caller's stream; the LM waits on its event. The LDS bin
 // fold (seed_bins_kernel) wherever its geometry applies — the fused kernel's seed fold,
 // so both paths give the same bits — the global fold / direct kernel otherwise.
-int seed_launch(int dev, const double* x, int64_t nrec, int64_t rec_stride, int R, int ndata, double w0, int L,
+template <typename XT>
+int seed_launch(int dev, const XT* x, int64_t nrec, int64_t rec_stride, int R, int ndata, double w0, int L,
                 const double* gdev, const dfmi::GuessInline& ginl, const double* jtab, const dfmi::LMConst& c,
                 double* out, int64_t out_ld, int64_t nbuf, int32_t* fitok, hipStream_t sst, bool seed_dc) {
   int rc;
@@ -953,23 +1007,27 @@ int seed_launch(int dev, const double* x, int64_t nrec, int64_t rec_stride, int 
   const size_t blds = ((size_t)2 * ndata * L + L + dfmi_row_stride(ndata)) * sizeof(double);
   if (L > 0 && bins_geometry(vec2, L, ndata, t_ds->lds_per_block, 1) && blds <= t_ds->lds_per_block) {
     const int nslot = (L + 127) / 128;
-    auto sk = ndata <= 12 ? (nslot <= 2 ? dfmi::seed_bins_kernel<12, 2> : nslot <= 4 ? dfmi::seed_bins_kernel<12, 4>
-                                                                                   : dfmi::seed_bins_kernel<12, 8>)
-            : ndata <= 16 ? (nslot <= 2 ? dfmi::seed_bins_kernel<16, 2> : nslot <= 4 ? dfmi::seed_bins_kernel<16, 4>
-                                                                                   : dfmi::seed_bins_kernel<16, 8>)
-                          : (nslot <= 2 ? dfmi::seed_bins_kernel<0, 2> : nslot <= 4 ? dfmi::seed_bins_kernel<0, 4>
-                                                                                  : dfmi::seed_bins_kernel<0, 8>);
+    auto sk = ndata <= 12   ? (nslot <= 2   ? dfmi::seed_bins_kernel<12, 2, XT>
+                               : nslot <= 4 ? dfmi::seed_bins_kernel<12, 4, XT>
+                                            : dfmi::seed_bins_kernel<12, 8, XT>)
+              : ndata <= 16 ? (nslot <= 2   ? dfmi::seed_bins_kernel<16, 2, XT>
+                               : nslot <= 4 ? dfmi::seed_bins_kernel<16, 4, XT>
+                                            : dfmi::seed_bins_kernel<16, 8, XT>)
+                            : (nslot <= 2   ? dfmi::seed_bins_kernel<0, 2, XT>
+                               : nslot <= 4 ? dfmi::seed_bins_kernel<0, 4, XT>
+                                            : dfmi::seed_bins_kernel<0, 8, XT>);
     hipLaunchKernelGGL(sk, dim3((unsigned)nrec), dim3(64), blds, sst, x, rec_stride, R, L, ndata, tab, gdev, ginl,
                        gdev ? 0 : 1, jtab, c, out, out_ld, nbuf, fitok, t_ds->probe, seed_dc ? 1 : 0);
   } else {
     void *qs, *ds_;
     if ((rc = workspace(dev, "qi_seed", (size_t)2 * ndata * nrec * 8, &qs))) return rc;
     if ((rc = workspace(dev, "dc_seed", (size_t)nrec * 8, &ds_))) return rc;
-    auto sk = ndata <= 12 ? dfmi::seed_kernel<12> : ndata <= 16 ? dfmi::seed_kernel<16>
-              : t_tune.lm_wide ? (t_tune.seed_wave_split ? dfmi::seed_kernel<dfmi::kWideNdF, 3>
-                                  : t_tune.lm_wide_fused ? dfmi::seed_kernel<dfmi::kWideNdF>
-                                                         : dfmi::seed_kernel<dfmi::kWideNd>)
-                               : dfmi::seed_kernel<0>;
+    constexpr int SF = dfmi::kSeedFlat;
+    auto sk = ndata <= 12 ? dfmi::seed_kernel<12, SF, XT> : ndata <= 16 ? dfmi::seed_kernel<16, SF, XT>
+              : t_tune.lm_wide ? (t_tune.seed_wave_split ? dfmi::seed_kernel<dfmi::kWideNdF, 3, XT>
+                                  : t_tune.lm_wide_fused ? dfmi::seed_kernel<dfmi::kWideNdF, SF, XT>
+                                                         : dfmi::seed_kernel<dfmi::kWideNd, SF, XT>)
+                               : dfmi::seed_kernel<0, SF, XT>;
     // the many-harmonic demodulation where its geometry holds (16-B rows, 128 <= L <= 256):
     // the bulk's own QI for buffer 0, and a fold with 10 wave loads in flight instead of the
     // cycle-aligned scalar fold against a global basis
@@ -988,7 +1046,8 @@ int seed_launch(int dev, const double* x, int64_t nrec, int64_t rec_stride, int 
   return DFMI_OK;
 }
 
-int nls_record_device(int dev, const double* x, int64_t nrec, int64_t rec_stride, int64_t nbuf, int R, int ndata,
+template <typename XT>
+int nls_record_device(int dev, const XT* x, int64_t nrec, int64_t rec_stride, int64_t nbuf, int R, int ndata,
                       double w0, int period, const double* init_guess_host, int parallel, int64_t nchunk,
                       const dfmi_lm_config& cfg, const dfmi::LMConst& c, double* out, int32_t* fitok,
                       hipStream_t st) {
@@ -1570,6 +1629,112 @@ int ekf_impl(const double* x, int64_t nrec, int64_t rec_stride, int64_t n_samp, 
 
 }  // namespace
 
+namespace {
+// Bodies of dfmi_demod / dfmi_demod_rows / dfmi_nls_record over the sample type XT (strides in
+// XT elements; host input is staged and copied as XT, never widened on the host).
+template <typename XT>
+int demod_impl(const XT* x, int64_t nseg, int64_t seg_stride, int32_t R, int32_t ndata, double w0,
+               int32_t period, double* qi, double* dc, int32_t mem, void* stream) {
+  CallScope cs(stream);
+  if (nseg < 0 || R <= 0 || ndata <= 0 || seg_stride < R) return fail(DFMI_ERR_ARG, "bad demod geometry");
+  if (nseg > 0 && (!x || !qi || !dc)) return fail(DFMI_ERR_ARG, "null pointer");
+  int dev;
+  int rc = ensure_init(&dev);
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if (mem == DFMI_MEM_DEVICE) return demod_device(dev, x, nseg, seg_stride, R, ndata, w0, period, qi, nseg, dc, st);
+  if (nseg == 0) return DFMI_OK;
+  const size_t xb = (size_t)((nseg - 1) * seg_stride + R) * sizeof(XT);
+  void *dx, *dq, *dd;
+  if ((rc = workspace(dev, "h_x", xb, &dx))) return rc;
+  if ((rc = workspace(dev, "h_qi", (size_t)2 * ndata * nseg * 8, &dq))) return rc;
+  if ((rc = workspace(dev, "h_dc", (size_t)nseg * 8, &dd))) return rc;
+  HIPCHK(hipMemcpyAsync(dx, x, xb, hipMemcpyHostToDevice, st));
+  rc = demod_device(dev, (const XT*)dx, nseg, seg_stride, R, ndata, w0, period, (double*)dq, nseg, (double*)dd, st);
+  if (rc) return rc;
+  HIPCHK(hipMemcpyAsync(qi, dq, (size_t)2 * ndata * nseg * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(dc, dd, (size_t)nseg * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return DFMI_OK;
+}
+
+template <typename XT>
+int demod_rows_impl(const XT* x, int64_t nseg, int64_t seg_stride, int32_t R, int32_t ndata, double w0,
+                    int32_t period, double* rows, int32_t mem, void* stream) {
+  CallScope cs(stream);
+  if (nseg < 0 || R <= 0 || ndata <= 0 || seg_stride < R) return fail(DFMI_ERR_ARG, "bad demod geometry");
+  if (nseg > 0 && (!x || !rows)) return fail(DFMI_ERR_ARG, "null pointer");
+  int dev;
+  int rc = ensure_init(&dev);
+  if (rc) return rc;
+  if (nseg == 0) return DFMI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t qs = dfmi_row_stride((int)ndata);
+  if (mem == DFMI_MEM_DEVICE) {
+    if (!rows_supported(dev, x, seg_stride, R, ndata, w0, period))
+      return fail(DFMI_ERR_UNSUPPORTED, "row layout needs 16-B rows and an even basis period 128 <= L <= 1024");
+    return demod_device(dev, x, nseg, seg_stride, R, ndata, w0, period, rows, qs, nullptr, st, true);
+  }
+  const size_t xb = (size_t)((nseg - 1) * seg_stride + R) * sizeof(XT);
+  void *dx, *dq;
+  if ((rc = workspace(dev, "h_x", xb, &dx))) return rc;
+  if ((rc = workspace(dev, "h_rows", (size_t)qs * nseg * 8, &dq))) return rc;
+  if (!rows_supported(dev, (const XT*)dx, seg_stride, R, ndata, w0, period))
+    return fail(DFMI_ERR_UNSUPPORTED, "row layout needs 16-B rows and an even basis period 128 <= L <= 1024");
+  HIPCHK(hipMemcpyAsync(dx, x, xb, hipMemcpyHostToDevice, st));
+  rc = demod_device(dev, (const XT*)dx, nseg, seg_stride, R, ndata, w0, period, (double*)dq, qs, nullptr, st, true);
+  if (rc) return rc;
+  HIPCHK(hipMemcpyAsync(rows, dq, (size_t)qs * nseg * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return DFMI_OK;
+}
+
+template <typename XT>
+int nls_record_impl(const XT* x, int64_t nrec, int64_t rec_stride, int64_t nbuf, int32_t R, int32_t ndata,
+                    double w0, int32_t period, const double* init_guess, int32_t parallel, int64_t nchunk,
+                    const dfmi_lm_config* cfg, double* out, int32_t* fitok, int32_t mem, void* stream) {
+  CallScope cs(stream);
+  if (nrec < 0 || nbuf < 0 || R <= 0 || ndata <= 0) return fail(DFMI_ERR_ARG, "bad record geometry");
+  if (nrec > 1 && rec_stride < nbuf * (int64_t)R) return fail(DFMI_ERR_ARG, "rec_stride < nbuf*R");
+  if (nrec * nbuf > 0 && (!x || !init_guess || !out || !fitok)) return fail(DFMI_ERR_ARG, "null pointer");
+  dfmi_lm_config dcfg;
+  if (!cfg) {
+    dfmi_lm_config_default(&dcfg);
+    cfg = &dcfg;
+  }
+  dfmi::LMConst c;
+  int rc = to_lmconst(cfg, &c);
+  if (rc) return rc;
+  int dev;
+  if ((rc = ensure_init(&dev))) return rc;
+  const int64_t nseg = nrec * nbuf;
+  if (nseg == 0) return DFMI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  if (mem == DFMI_MEM_DEVICE)
+    return nls_record_device(dev, x, nrec, rec_stride, nbuf, R, ndata, w0, period, init_guess, parallel, nchunk, *cfg,
+                             c, out, fitok, st);
+  const int64_t rs = (nrec > 1) ? rec_stride : nbuf * (int64_t)R;
+  const size_t xb = (size_t)((nrec - 1) * rs + nbuf * (int64_t)R) * sizeof(XT);
+  void *dx, *dout, *dst;
+  if ((rc = workspace(dev, "h_x", xb, &dx))) return rc;
+  if ((rc = workspace(dev, "h_out", (size_t)6 * nseg * 8, &dout))) return rc;
+  if ((rc = workspace(dev, "h_status", (size_t)nseg * 4, &dst))) return rc;
+  HIPCHK(hipMemcpyAsync(dx, x, xb, hipMemcpyHostToDevice, st));
+  rc = nls_record_device(dev, (const XT*)dx, nrec, rs, nbuf, R, ndata, w0, period, init_guess, parallel, nchunk,
+                         *cfg, c, (double*)dout, (int32_t*)dst, st);
+  if (rc) return rc;
+  HIPCHK(hipMemcpyAsync(out, dout, (size_t)6 * nseg * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(fitok, dst, (size_t)nseg * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return DFMI_OK;
+}
+
+
+int bad_xtype(int32_t xtype) {
+  return xtype != DFMI_F64 && xtype != DFMI_F32;
+}
+}  // namespace
+
 extern "C" {
 
 void dfmi_lm_config_default(dfmi_lm_config* cfg) {
@@ -1718,62 +1883,50 @@ int dfmi_release_workspaces(void) {
 
 int dfmi_demod(const double* x, int64_t nseg, int64_t seg_stride, int32_t R, int32_t ndata, double w0,
                int32_t period, double* qi, double* dc, int32_t mem, void* stream) {
-  CallScope cs(stream);
-  if (nseg < 0 || R <= 0 || ndata <= 0 || seg_stride < R) return fail(DFMI_ERR_ARG, "bad demod geometry");
-  if (nseg > 0 && (!x || !qi || !dc)) return fail(DFMI_ERR_ARG, "null pointer");
-  int dev;
-  int rc = ensure_init(&dev);
-  if (rc) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  if (mem == DFMI_MEM_DEVICE) return demod_device(dev, x, nseg, seg_stride, R, ndata, w0, period, qi, nseg, dc, st);
-  if (nseg == 0) return DFMI_OK;
-  const size_t xb = (size_t)((nseg - 1) * seg_stride + R) * sizeof(double);
-  void *dx, *dq, *dd;
-  if ((rc = workspace(dev, "h_x", xb, &dx))) return rc;
-  if ((rc = workspace(dev, "h_qi", (size_t)2 * ndata * nseg * 8, &dq))) return rc;
-  if ((rc = workspace(dev, "h_dc", (size_t)nseg * 8, &dd))) return rc;
-  HIPCHK(hipMemcpyAsync(dx, x, xb, hipMemcpyHostToDevice, st));
-  rc = demod_device(dev, (const double*)dx, nseg, seg_stride, R, ndata, w0, period, (double*)dq, nseg, (double*)dd, st);
-  if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(qi, dq, (size_t)2 * ndata * nseg * 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(dc, dd, (size_t)nseg * 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return DFMI_OK;
+  return demod_impl<double>(x, nseg, seg_stride, R, ndata, w0, period, qi, dc, mem, stream);
+}
+
+int dfmi_demod_typed(const void* x, int32_t xtype, int64_t nseg, int64_t seg_stride, int32_t R, int32_t ndata,
+                     double w0, int32_t period, double* qi, double* dc, int32_t mem, void* stream) {
+  if (bad_xtype(xtype)) return fail(DFMI_ERR_ARG, "unknown sample type");
+  if (xtype == DFMI_F64) return dfmi_demod((const double*)x, nseg, seg_stride, R, ndata, w0, period, qi, dc, mem, stream);
+  return demod_impl<float>((const float*)x, nseg, seg_stride, R, ndata, w0, period, qi, dc, mem, stream);
+}
+
+int dfmi_demod_rows(const double* x, int64_t nseg, int64_t seg_stride, int32_t R, int32_t ndata, double w0,
+                    int32_t period, double* rows, int32_t mem, void* stream) {
+  return demod_rows_impl<double>(x, nseg, seg_stride, R, ndata, w0, period, rows, mem, stream);
+}
+
+int dfmi_demod_rows_typed(const void* x, int32_t xtype, int64_t nseg, int64_t seg_stride, int32_t R, int32_t ndata,
+                          double w0, int32_t period, double* rows, int32_t mem, void* stream) {
+  if (bad_xtype(xtype)) return fail(DFMI_ERR_ARG, "unknown sample type");
+  if (xtype == DFMI_F64) return dfmi_demod_rows((const double*)x, nseg, seg_stride, R, ndata, w0, period, rows, mem, stream);
+  return demod_rows_impl<float>((const float*)x, nseg, seg_stride, R, ndata, w0, period, rows, mem, stream);
+}
+
+int dfmi_nls_record(const double* x, int64_t nrec, int64_t rec_stride, int64_t nbuf, int32_t R, int32_t ndata,
+                    double w0, int32_t period, const double* init_guess, int32_t parallel, int64_t nchunk,
+                    const dfmi_lm_config* cfg, double* out, int32_t* fitok, int32_t mem, void* stream) {
+  return nls_record_impl<double>(x, nrec, rec_stride, nbuf, R, ndata, w0, period, init_guess, parallel, nchunk, cfg, out,
+                                 fitok, mem, stream);
+}
+
+int dfmi_nls_record_typed(const void* x, int32_t xtype, int64_t nrec, int64_t rec_stride, int64_t nbuf, int32_t R,
+                          int32_t ndata, double w0, int32_t period, const double* init_guess, int32_t parallel,
+                          int64_t nchunk, const dfmi_lm_config* cfg, double* out, int32_t* fitok, int32_t mem,
+                          void* stream) {
+  if (bad_xtype(xtype)) return fail(DFMI_ERR_ARG, "unknown sample type");
+  if (xtype == DFMI_F64)
+    return dfmi_nls_record((const double*)x, nrec, rec_stride, nbuf, R, ndata, w0, period, init_guess, parallel, nchunk,
+                           cfg, out, fitok, mem, stream);
+  return nls_record_impl<float>((const float*)x, nrec, rec_stride, nbuf, R, ndata, w0, period, init_guess, parallel,
+                                nchunk, cfg, out, fitok, mem, stream);
 }
 
 int32_t dfmi_qi_row_stride(int32_t ndata) { return ndata > 0 ? dfmi_row_stride((int)ndata) : 0; }
 
 int32_t dfmi_qi_row_dc(int32_t ndata) { return ndata > 0 ? dfmi_row_dc((int)ndata) : 0; }
-
-int dfmi_demod_rows(const double* x, int64_t nseg, int64_t seg_stride, int32_t R, int32_t ndata, double w0,
-                    int32_t period, double* rows, int32_t mem, void* stream) {
-  CallScope cs(stream);
-  if (nseg < 0 || R <= 0 || ndata <= 0 || seg_stride < R) return fail(DFMI_ERR_ARG, "bad demod geometry");
-  if (nseg > 0 && (!x || !rows)) return fail(DFMI_ERR_ARG, "null pointer");
-  int dev;
-  int rc = ensure_init(&dev);
-  if (rc) return rc;
-  if (nseg == 0) return DFMI_OK;
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t qs = dfmi_row_stride((int)ndata);
-  if (mem == DFMI_MEM_DEVICE) {
-    if (!rows_supported(dev, x, seg_stride, R, ndata, w0, period))
-      return fail(DFMI_ERR_UNSUPPORTED, "row layout needs 16-B rows and an even basis period 128 <= L <= 1024");
-    return demod_device(dev, x, nseg, seg_stride, R, ndata, w0, period, rows, qs, nullptr, st, true);
-  }
-  const size_t xb = (size_t)((nseg - 1) * seg_stride + R) * sizeof(double);
-  void *dx, *dq;
-  if ((rc = workspace(dev, "h_x", xb, &dx))) return rc;
-  if ((rc = workspace(dev, "h_rows", (size_t)qs * nseg * 8, &dq))) return rc;
-  if (!rows_supported(dev, (const double*)dx, seg_stride, R, ndata, w0, period))
-    return fail(DFMI_ERR_UNSUPPORTED, "row layout needs 16-B rows and an even basis period 128 <= L <= 1024");
-  HIPCHK(hipMemcpyAsync(dx, x, xb, hipMemcpyHostToDevice, st));
-  rc = demod_device(dev, (const double*)dx, nseg, seg_stride, R, ndata, w0, period, (double*)dq, qs, nullptr, st, true);
-  if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(rows, dq, (size_t)qs * nseg * 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return DFMI_OK;
-}
 
 int dfmi_lm(const double* qi, int64_t nseg, int32_t ndata, const double* guess, int32_t guess_per_segment,
             int64_t nchunk, const dfmi_lm_config* cfg, double* params, double* ssq, int32_t* status, int32_t mem,
@@ -1824,45 +1977,6 @@ int dfmi_lm(const double* qi, int64_t nseg, int32_t ndata, const double* guess, 
   HIPCHK(hipMemcpyAsync(ssq, o + 5 * nseg, (size_t)nseg * 8, kind, st));
   HIPCHK(hipMemcpyAsync(status, dst, (size_t)nseg * 4, kind, st));
   if (mem != DFMI_MEM_DEVICE) HIPCHK(hipStreamSynchronize(st));
-  return DFMI_OK;
-}
-
-int dfmi_nls_record(const double* x, int64_t nrec, int64_t rec_stride, int64_t nbuf, int32_t R, int32_t ndata,
-                    double w0, int32_t period, const double* init_guess, int32_t parallel, int64_t nchunk,
-                    const dfmi_lm_config* cfg, double* out, int32_t* fitok, int32_t mem, void* stream) {
-  CallScope cs(stream);
-  if (nrec < 0 || nbuf < 0 || R <= 0 || ndata <= 0) return fail(DFMI_ERR_ARG, "bad record geometry");
-  if (nrec > 1 && rec_stride < nbuf * (int64_t)R) return fail(DFMI_ERR_ARG, "rec_stride < nbuf*R");
-  if (nrec * nbuf > 0 && (!x || !init_guess || !out || !fitok)) return fail(DFMI_ERR_ARG, "null pointer");
-  dfmi_lm_config dcfg;
-  if (!cfg) {
-    dfmi_lm_config_default(&dcfg);
-    cfg = &dcfg;
-  }
-  dfmi::LMConst c;
-  int rc = to_lmconst(cfg, &c);
-  if (rc) return rc;
-  int dev;
-  if ((rc = ensure_init(&dev))) return rc;
-  const int64_t nseg = nrec * nbuf;
-  if (nseg == 0) return DFMI_OK;
-  hipStream_t st = (hipStream_t)stream;
-  if (mem == DFMI_MEM_DEVICE)
-    return nls_record_device(dev, x, nrec, rec_stride, nbuf, R, ndata, w0, period, init_guess, parallel, nchunk, *cfg,
-                             c, out, fitok, st);
-  const int64_t rs = (nrec > 1) ? rec_stride : nbuf * (int64_t)R;
-  const size_t xb = (size_t)((nrec - 1) * rs + nbuf * (int64_t)R) * 8;
-  void *dx, *dout, *dst;
-  if ((rc = workspace(dev, "h_x", xb, &dx))) return rc;
-  if ((rc = workspace(dev, "h_out", (size_t)6 * nseg * 8, &dout))) return rc;
-  if ((rc = workspace(dev, "h_status", (size_t)nseg * 4, &dst))) return rc;
-  HIPCHK(hipMemcpyAsync(dx, x, xb, hipMemcpyHostToDevice, st));
-  rc = nls_record_device(dev, (const double*)dx, nrec, rs, nbuf, R, ndata, w0, period, init_guess, parallel, nchunk,
-                         *cfg, c, (double*)dout, (int32_t*)dst, st);
-  if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(out, dout, (size_t)6 * nseg * 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(fitok, dst, (size_t)nseg * 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
   return DFMI_OK;
 }
 

@@ -8,6 +8,9 @@
 // SIDE stream, concurrently with the bulk demodulation on the main stream, and
 // the bulk LM waits on an event: the seed costs no wall time as long as it is
 // shorter than the bulk demodulation.
+//
+// Every seed kernel reads its record's buffer 0 as samples of type XT (demod.h SampleT:
+// double, or float widened on load), so a float record is seeded without a widened copy.
 #pragma once
 #include "demod.h"
 #include "lm.h"
@@ -37,8 +40,8 @@ constexpr int kSeedFlat = 2;
 // SFLAT: the seed's descent — kSeedFlat (8 rungs by 8-lane groups, every group the same fit) or,
 // beyond 16 harmonics (tuning seed_wave_split), 3: the wave's 64 lanes as 8 rungs x 8 harmonic
 // shares (lm.h PartFullEval), one fit.
-template <int NDMAX, int SFLAT = kSeedFlat>
-__global__ __launch_bounds__(64) void seed_kernel(const double* __restrict__ x, int64_t rec_stride, int R, int L,
+template <int NDMAX, int SFLAT = kSeedFlat, typename XT = double>
+__global__ __launch_bounds__(64) void seed_kernel(const XT* __restrict__ x, int64_t rec_stride, int R, int L,
                                                   int ndata, double w0, const double* __restrict__ tab,
                                                   double* __restrict__ qis, double* __restrict__ dcs, int64_t nrec,
                                                   const double* __restrict__ guess, GuessInline ginl, int use_inline,
@@ -49,10 +52,10 @@ __global__ __launch_bounds__(64) void seed_kernel(const double* __restrict__ x, 
   extern __shared__ __attribute__((aligned(16))) double ybin_dyn[];
   const int64_t r = blockIdx.x;
   const int lane = threadIdx.x;
-  const double* __restrict__ xs = x + r * rec_stride;
-  if (tabT) wide_seed_segment(xs, R, L, ndata, tabT, no, ybin_dyn, lane, qis, nrec, r, dcs);
-  else if (L > 0) fold_segment<1, 16>(xs, R, L, ndata, tab, lane, qis, nrec, r, dcs);
-  else direct_segment(xs, R, ndata, w0, lane, qis, nrec, r, dcs);
+  const XT* __restrict__ xs = x + r * rec_stride;
+  if (tabT) wide_seed_segment<XT>(xs, R, L, ndata, tabT, no, ybin_dyn, lane, qis, nrec, r, dcs);
+  else if (L > 0) fold_segment<1, 16, 8, true, XT>(xs, R, L, ndata, tab, lane, qis, nrec, r, dcs);
+  else direct_segment<XT>(xs, R, ndata, w0, lane, qis, nrec, r, dcs);
   __syncthreads();  // QI of this record (global, same workgroup) visible to the wave
   // ... and into LDS for the fit: its evaluations read every QI value once per harmonic, and
   // from global memory each read waited a round trip under the bulk demodulation's load
@@ -97,8 +100,8 @@ __global__ __launch_bounds__(64) void seed_kernel(const double* __restrict__ x, 
 // demodulation saturates HBM (seed_kernel, with QI in global memory and a
 // 128-VGPR cap, took as long as the whole demodulation beside it:
 // profiles/r01b_seed_timeline.txt). Same QI, dc and fit as the bulk path.
-template <int NDMAX, int MAXSLOT>
-__global__ __launch_bounds__(64) void seed_bins_kernel(const double* __restrict__ x, int64_t rec_stride, int R, int L,
+template <int NDMAX, int MAXSLOT, typename XT = double>
+__global__ __launch_bounds__(64) void seed_bins_kernel(const XT* __restrict__ x, int64_t rec_stride, int R, int L,
                                                        int ndata, const double* __restrict__ tab,
                                                        const double* __restrict__ guess, GuessInline ginl,
                                                        int use_inline, const double* __restrict__ jtab, LMConst c,
@@ -148,8 +151,8 @@ __global__ __launch_bounds__(64) void seed_bins_kernel(const double* __restrict_
     pbase[j] = 2 * (lane + 64 * j);
     pval[j] = (j < nslot) && (pbase[j] < L);
   }
-  bins_segment<MAXSLOT, 32, false, kHarmBlock, true, 0, true>(x + r * rec_stride, R, L, ndata, sh, ybin, lane, pval, pbase,
-                                                        row, 0, 0, nullptr);
+  bins_segment<MAXSLOT, 32, false, kHarmBlock, true, 0, true, XT>(x + r * rec_stride, R, L, ndata, sh, ybin, lane, pval,
+                                                                  pbase, row, 0, 0, nullptr);
   __syncthreads();
   const uint64_t t_fold = __builtin_amdgcn_s_memrealtime();
   double p[4] = {0.0, 0.0, 0.0, 0.0};
@@ -207,15 +210,15 @@ namespace dfmi {
 #else
 #define DFMI_SEED_BOUNDS __launch_bounds__(kBlockThreads)
 #endif
-template <int MAXSLOT, int NDMAX, int PFN = 0, int LOADS = 8>
+template <int MAXSLOT, int NDMAX, int PFN = 0, int LOADS = 8, typename XT = double>
 __global__ DFMI_SEED_BOUNDS void demod_seed_bins_kernel(
-    const double* __restrict__ x, int64_t nseg, int64_t rec_stride, int64_t nrec, int R, int L, int ndata,
+    const XT* __restrict__ x, int64_t nseg, int64_t rec_stride, int64_t nrec, int R, int L, int ndata,
     const double* __restrict__ tab, double* __restrict__ rows, int64_t row_ld, const double* __restrict__ guess,
     GuessInline ginl, int use_inline, const double* __restrict__ jtab, LMConst c, double* __restrict__ out,
     int64_t out_ld, int64_t nbuf, int32_t* __restrict__ status, uint64_t* __restrict__ probe) {
   if ((int64_t)blockIdx.x >= nrec) {
-    bins_kernel_body<MAXSLOT, LOADS, true, PFN>(x, nseg, (int64_t)R, R, L, ndata, tab, rows, row_ld, nullptr, probe,
-                                                (int)nrec);
+    bins_kernel_body<MAXSLOT, LOADS, true, PFN, XT>(x, nseg, (int64_t)R, R, L, ndata, tab, rows, row_ld, nullptr, probe,
+                                                    (int)nrec);
     return;
   }
   const uint64_t t_in = __builtin_amdgcn_s_memrealtime();
@@ -256,8 +259,8 @@ __global__ DFMI_SEED_BOUNDS void demod_seed_bins_kernel(
       pbase[j] = 2 * (lane + 64 * j);
       pval[j] = (j < nslot) && (pbase[j] < L);
     }
-    bins_segment<MAXSLOT, 32, false, kHarmBlock, true, 0, true>(x + r * rec_stride, R, L, ndata, sh, ybin, lane, pval, pbase,
-                                                          row, 0, 0, nullptr);
+    bins_segment<MAXSLOT, 32, false, kHarmBlock, true, 0, true, XT>(x + r * rec_stride, R, L, ndata, sh, ybin, lane, pval,
+                                                                    pbase, row, 0, 0, nullptr);
   }
   __syncthreads();
   const uint64_t t_fold = __builtin_amdgcn_s_memrealtime();

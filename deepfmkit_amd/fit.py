@@ -69,17 +69,40 @@ def _lm_config_build() -> _lib.LMConfig:
 def demodulate(buffers, ndata: int, w0: float, period: int = 0):
     """QI of every row of `buffers` (nseg, R) float64 -> (QI (nseg, 2*ndata), dc (nseg,)).
 
-    QI row layout is the reference's [Q_1..Q_ndata, I_1..I_ndata] (fitters.py:45-49)."""
+    QI row layout is the reference's [Q_1..Q_ndata, I_1..I_ndata] (fitters.py:45-49).
+    A float32 array is sent as it is (dfmi_demod_typed: the kernels widen on load, the same
+    bits as for the widened array); every other dtype is widened to float64 here."""
     lib = _lib.load()
-    x = np.ascontiguousarray(buffers, dtype=np.float64)
+    f32 = isinstance(buffers, np.ndarray) and buffers.dtype == np.float32
+    x = np.ascontiguousarray(buffers, dtype=np.float32 if f32 else np.float64)
     if x.ndim != 2:
         raise ValueError("buffers must be (nseg, R)")
     nseg, R = x.shape
     qi_cm = np.empty((2 * ndata, nseg))
     dc = np.empty(nseg)
-    _lib.check(lib.dfmi_demod(_lib.ptr(x), nseg, R, R, ndata, float(w0), int(period), _lib.ptr(qi_cm),
-                              _lib.ptr(dc), _lib.DFMI_MEM_HOST, None), "dfmi_demod")
+    if f32:
+        _lib.check(lib.dfmi_demod_typed(_lib.ptr(x), _lib.DFMI_F32, nseg, R, R, ndata, float(w0), int(period),
+                                        _lib.ptr(qi_cm), _lib.ptr(dc), _lib.DFMI_MEM_HOST, None), "dfmi_demod_typed")
+    else:
+        _lib.check(lib.dfmi_demod(_lib.ptr(x), nseg, R, R, ndata, float(w0), int(period), _lib.ptr(qi_cm),
+                                  _lib.ptr(dc), _lib.DFMI_MEM_HOST, None), "dfmi_demod")
     return np.ascontiguousarray(qi_cm.T), dc
+
+
+def demodulate_rows(buffers, ndata: int, w0: float, period: int = 0):
+    """The record pipeline's row layout (include/dfmi.h dfmi_demod_rows) of every row of
+    `buffers` (nseg, R), float64 or float32 as in demodulate -> rows (nseg, dfmi_qi_row_stride)."""
+    lib = _lib.load()
+    f32 = isinstance(buffers, np.ndarray) and buffers.dtype == np.float32
+    x = np.ascontiguousarray(buffers, dtype=np.float32 if f32 else np.float64)
+    if x.ndim != 2:
+        raise ValueError("buffers must be (nseg, R)")
+    nseg, R = x.shape
+    rows = np.empty((nseg, lib.dfmi_qi_row_stride(ndata)))
+    _lib.check(lib.dfmi_demod_rows_typed(_lib.ptr(x), _lib.DFMI_F32 if f32 else _lib.DFMI_F64, nseg, R, R, ndata,
+                                         float(w0), int(period), _lib.ptr(rows), _lib.DFMI_MEM_HOST, None),
+               "dfmi_demod_rows_typed")
+    return rows
 
 
 def fit_batch(ndata: int, qi, guess):

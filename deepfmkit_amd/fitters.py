@@ -72,6 +72,14 @@ def _on_device(x):
     return torch.cuda.device(x.device)
 
 
+def _host_samples(x):
+    """A host record as the library takes it: a float32 array stays float32 (the typed entry
+    point reads it natively: half the bytes over the host link), anything else is widened to
+    float64 as the reference's arithmetic would."""
+    x = np.asarray(x)
+    return x if x.dtype == np.float32 else np.asarray(x, dtype=np.float64)
+
+
 def w0_of(f_mod, f_samp):
     """fitters.py:39 / 376 / 434: w0 = 2*pi*f_mod/f_samp (same operation order)."""
     return 2.0 * np.pi * f_mod / f_samp
@@ -82,10 +90,12 @@ def nls_records(records, f_samp, f_mod, R, nbuf, ndata=10, init_guess=(1.6, 6.0,
     """Run the StandardNLSFitter pipeline on one or more equal-length records in ONE
     GPU call (config 3: several channels as one batch).
 
-    records: list of 1-D float64 arrays (host) or CUDA tensors, or a 2-D array/tensor
-    (nrec, >= nbuf*R). init_guess: (4,) shared or (nrec, 4). Returns (cols (6, nrec*nbuf)
-    in the order amp, m, phi, psi, dc, ssq; fitok (nrec*nbuf,)), as numpy arrays for host
-    input and as CUDA tensors for device input."""
+    records: list of 1-D float64 or float32 arrays (host) or CUDA tensors, or a 2-D array/tensor
+    (nrec, >= nbuf*R). float32 records go to dfmi_nls_record_typed as they are (the kernels widen
+    on load: the same bits as for the widened record); host arrays of any other dtype are widened
+    to float64, device tensors of any other dtype are refused. init_guess: (4,) shared or
+    (nrec, 4). Returns (cols (6, nrec*nbuf) in the order amp, m, phi, psi, dc, ssq; fitok
+    (nrec*nbuf,)), as numpy arrays for host input and as CUDA tensors for device input."""
     lib = _lib.load()
     w0 = w0_of(f_mod, f_samp)
     if isinstance(records, (list, tuple)):
@@ -93,11 +103,15 @@ def nls_records(records, f_samp, f_mod, R, nbuf, ndata=10, init_guess=(1.6, 6.0,
             import torch
             x = torch.stack([r[: nbuf * R] for r in records]).contiguous()
         else:
-            x = np.ascontiguousarray(np.stack([np.asarray(r, np.float64)[: nbuf * R] for r in records]))
+            recs = [_host_samples(r) for r in records]
+            dt = np.float32 if all(r.dtype == np.float32 for r in recs) else np.float64
+            x = np.ascontiguousarray(np.stack([r[: nbuf * R] for r in recs]), dtype=dt)
     else:
         x = records
+    if not _is_device_tensor(x):
+        x = np.ascontiguousarray(_host_samples(x))
     nrec = int(x.shape[0])
-    rec_stride = int(x.stride(0)) if _is_device_tensor(x) else int(x.strides[0] // 8)
+    rec_stride = int(x.stride(0)) if _is_device_tensor(x) else int(x.strides[0] // x.itemsize)
     g = np.asarray(init_guess, dtype=np.float64)
     g = np.ascontiguousarray(np.broadcast_to(g, (nrec, 4)) if g.ndim == 1 else g)
     nchunk = (nbuf - 1) if n_cores is None else max(1, min(int(n_cores), nbuf))
@@ -105,8 +119,9 @@ def nls_records(records, f_samp, f_mod, R, nbuf, ndata=10, init_guess=(1.6, 6.0,
     nseg = nrec * nbuf
     if _is_device_tensor(x):
         import torch
-        if x.dtype != torch.float64 or x.stride(-1) != 1:
-            raise ValueError("device records must be contiguous float64 rows")
+        if x.dtype not in (torch.float64, torch.float32) or x.stride(-1) != 1:
+            raise ValueError("device records must be contiguous float64 or float32 rows")
+        xtype = _lib.DFMI_F32 if x.dtype == torch.float32 else _lib.DFMI_F64
         # rows 0..5 of one (7, nseg) block: the six result columns; row 6 receives fitok as
         # int64 (frame_from), so the whole result leaves the device in one copy
         out = torch.empty((7, nseg), dtype=torch.float64, device=x.device)[:6]
@@ -114,18 +129,28 @@ def nls_records(records, f_samp, f_mod, R, nbuf, ndata=10, init_guess=(1.6, 6.0,
         ok = torch.empty(nseg, dtype=torch.int32, device=x.device)
         mark("alloc")
         with _on_device(x):
-            rc = lib.dfmi_nls_record(x.data_ptr(), nrec, rec_stride, nbuf, R, ndata, w0, 0, _lib.ptr(g),
-                                     1 if parallel else 0, max(nchunk, 1), cfg, out.data_ptr(), ok.data_ptr(),
-                                     _lib.DFMI_MEM_DEVICE, _torch_stream(x.device))
+            if xtype == _lib.DFMI_F64:
+                rc = lib.dfmi_nls_record(x.data_ptr(), nrec, rec_stride, nbuf, R, ndata, w0, 0, _lib.ptr(g),
+                                         1 if parallel else 0, max(nchunk, 1), cfg, out.data_ptr(), ok.data_ptr(),
+                                         _lib.DFMI_MEM_DEVICE, _torch_stream(x.device))
+            else:
+                rc = lib.dfmi_nls_record_typed(x.data_ptr(), xtype, nrec, rec_stride, nbuf, R, ndata, w0, 0,
+                                               _lib.ptr(g), 1 if parallel else 0, max(nchunk, 1), cfg,
+                                               out.data_ptr(), ok.data_ptr(), _lib.DFMI_MEM_DEVICE,
+                                               _torch_stream(x.device))
         _lib.check(rc, "dfmi_nls_record")
         mark("enqueue")
         return out, ok
-    x = np.ascontiguousarray(x, dtype=np.float64)
     out = np.empty((6, nseg))
     ok = np.empty(nseg, dtype=np.int32)
-    rc = lib.dfmi_nls_record(_lib.ptr(x), nrec, rec_stride, nbuf, R, ndata, w0, 0, _lib.ptr(g),
-                             1 if parallel else 0, max(nchunk, 1), cfg, _lib.ptr(out), _lib.ptr(ok),
-                             _lib.DFMI_MEM_HOST, None)
+    if x.dtype == np.float32:
+        rc = lib.dfmi_nls_record_typed(_lib.ptr(x), _lib.DFMI_F32, nrec, rec_stride, nbuf, R, ndata, w0, 0,
+                                       _lib.ptr(g), 1 if parallel else 0, max(nchunk, 1), cfg, _lib.ptr(out),
+                                       _lib.ptr(ok), _lib.DFMI_MEM_HOST, None)
+    else:
+        rc = lib.dfmi_nls_record(_lib.ptr(x), nrec, rec_stride, nbuf, R, ndata, w0, 0, _lib.ptr(g),
+                                 1 if parallel else 0, max(nchunk, 1), cfg, _lib.ptr(out), _lib.ptr(ok),
+                                 _lib.DFMI_MEM_HOST, None)
     _lib.check(rc, "dfmi_nls_record")
     return out, ok
 
@@ -138,7 +163,8 @@ def nls_record_devices(x, f_samp, f_mod, R, nbuf, devices, ndata=10, init_guess=
     fits the seed buffer itself, as every reference Pool chunk receives it (no exchange) —
     and the rows come back in record order. All devices' work is enqueued before any result
     is read, so the GPUs run concurrently; each shard's samples go host -> device (or
-    device -> device) once. x: 1-D float64 numpy array or CUDA tensor (>= nbuf*R samples).
+    device -> device) once. x: 1-D float64 or float32 numpy array or CUDA tensor (>= nbuf*R
+    samples); the shards are allocated in the record's dtype.
     Returns (cols (6, nbuf) numpy in the order amp, m, phi, psi, dc, ssq; fitok (nbuf,)),
     bit-identical to one nls_records call (segments are independent once the seed is known).
     Same-device entries are allowed (shards then run one after another on that GPU)."""
@@ -153,13 +179,14 @@ def nls_record_devices(x, f_samp, f_mod, R, nbuf, devices, ndata=10, init_guess=
         parts = [np.arange(1, 1)]
     host = not _is_device_tensor(x)
     if host:
-        x = np.asarray(x, dtype=np.float64)
+        x = _host_samples(x)
+    xdt = torch.float32 if x.dtype == (np.float32 if host else torch.float32) else torch.float64
     pending = []
     for dev, idx in zip(devs, parts):
         b0, b1 = (int(idx[0]), int(idx[-1]) + 1) if idx.size else (1, 1)
         n_s = 1 + (b1 - b0)
         with torch.cuda.device(dev):
-            xs = torch.empty(n_s * R, dtype=torch.float64, device=dev)
+            xs = torch.empty(n_s * R, dtype=xdt, device=dev)
             if host:
                 xs[:R].copy_(torch.from_numpy(x[:R]))
                 if b1 > b0:
@@ -304,7 +331,7 @@ class StandardNLSFitter(BaseFitter):
             # the reference reshapes the whole column with reshape(-1, R) (fitters.py:375, 412)
             raise ValueError(f"cannot reshape array of size {N} into shape ({R})")
         if not _is_device_tensor(x):
-            x = np.asarray(x, dtype=np.float64)
+            x = _host_samples(x)
         devices = kwargs.get("devices")
         if devices is not None and (not parallel or kwargs.get("n_cores") is not None):
             # a device list spreads the chunk-size-1 parallel fit only; a warm-start chain

@@ -75,15 +75,26 @@ def read_columns(path, cols, mode, skip=HEADER_LINES):
     return out, int(ncols.value)
 
 
-def read_raw(path, device=None):
+def read_raw(path, device=None, dtype=None):
     """load_raw's data (core.py:279-280): channel c = column c of every row after the
     13 header lines, pandas sep=' ' semantics. Returns (header dict, list of channel
-    arrays); with `device` ("cuda:0", ...) the channels are torch tensors there."""
+    arrays); with `device` ("cuda:0", ...) the channels are torch tensors there, float64
+    or, with dtype="float32" (only valid together with `device`), cast once to float32 on
+    the host before the copy."""
+    if dtype is not None:
+        if hasattr(dtype, "is_floating_point"):  # a torch dtype: by its name
+            dtype = str(dtype).split(".")[-1]
+        if np.dtype(dtype) not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise ValueError(f"dtype must be float32 or float64, got {dtype!r}")
+        if device is None:
+            raise ValueError("dtype is only valid together with device (host data stays float64)")
     hdr = parse_header(path, RAW)
     data, _ = read_columns(path, list(range(hdr["channr"])), SINGLE_SPACE)
     if device is None:
         return hdr, [data[c] for c in range(hdr["channr"])]
     import torch
+    if dtype is not None and np.dtype(dtype) == np.float32:
+        data = data.astype(np.float32)
     host = torch.from_numpy(data).pin_memory()
     dev = host.to(device, non_blocking=True)
     torch.cuda.current_stream(dev.device).synchronize()

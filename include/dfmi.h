@@ -127,6 +127,35 @@ int dfmi_nls_record(const double* x, int64_t nrec, int64_t rec_stride, int64_t n
                     double w0, int32_t period, const double* init_guess, int32_t parallel, int64_t nchunk,
                     const dfmi_lm_config* cfg, double* out, int32_t* fitok, int32_t mem, void* stream);
 
+/* Typed sample input. dfmi_demod_typed, dfmi_demod_rows_typed and dfmi_nls_record_typed are
+ * dfmi_demod, dfmi_demod_rows and dfmi_nls_record with the samples x of type `xtype`:
+ *   DFMI_F64   double: forwards to the untyped function (same kernel, same bits)
+ *   DFMI_F32   float:  the kernels load float and widen in registers
+ * Every other argument, the outputs (float64) and the layouts are those of the untyped
+ * function; strides are in ELEMENTS of the sample type. An unknown xtype is DFMI_ERR_ARG.
+ * float -> double is exact and every phase bin still receives its samples in ascending time,
+ * so a float record gives, bit for bit, what the untyped function gives on the same record
+ * widened to double. With DFMI_MEM_HOST the record is staged and copied as float (half the
+ * bytes over the host link); it is never widened on the host.
+ * The bin, fused seed + bin, many-harmonic and seed kernels read float themselves; their
+ * vector-pair precondition is rows aligned to 8 B at an even stride (16 B for double). The
+ * branches left (the fold kernel: L < 128, odd L or rows without pair alignment; the direct
+ * kernel) widen the rows into a device workspace of 8 B per sample first and run the double
+ * kernel on it. dfmi_last_demod_kernel() says which: the double call's string followed by
+ * " [f32]" (read natively) or " [f32 widened]" (the fallback).
+ * Float64 only: dfmi_ekf, dfmi_ekf_fit, dfmi_wdfmi_fit (main and witness records),
+ * dfmi_record_moments, and the synthesis calls' outputs (dfmi_synth_asd, dfmi_synth_snr). */
+#define DFMI_F64 0
+#define DFMI_F32 1
+int dfmi_demod_typed(const void* x, int32_t xtype, int64_t nseg, int64_t seg_stride, int32_t R, int32_t ndata,
+                     double w0, int32_t period, double* qi, double* dc, int32_t mem, void* stream);
+int dfmi_demod_rows_typed(const void* x, int32_t xtype, int64_t nseg, int64_t seg_stride, int32_t R, int32_t ndata,
+                          double w0, int32_t period, double* rows, int32_t mem, void* stream);
+int dfmi_nls_record_typed(const void* x, int32_t xtype, int64_t nrec, int64_t rec_stride, int64_t nbuf, int32_t R,
+                          int32_t ndata, double w0, int32_t period, const double* init_guess, int32_t parallel,
+                          int64_t nchunk, const dfmi_lm_config* cfg, double* out, int32_t* fitok, int32_t mem,
+                          void* stream);
+
 /* Per-sample EKF (fitters.py:214-320) over nrec independent channels, each a serial
  * chain over its samples: up to 16 x CUs channels one 16-lane DPP row per channel (4 per
  * wave; ekf_rot_kernel with sin / cos by rotation between anchors when R % 4 == 0, else
@@ -430,7 +459,9 @@ const char* dfmi_version(void);
  * build), e.g. "demod_seed_bins_kernel<2,12,4,10> (prefetch 4)" (the record pipeline's
  * fused seed + demodulation), "demod_bins_kernel<2,10,rows,4> (prefetch 4)" (dfmi_demod_rows),
  * "ekf_rot_kernel", "ekf_row_kernel", "ekf_lane_rot_kernel", "ekf_kernel" ("" before the
- * first one). Diagnostics/profiling. */
+ * first one). A typed call on float samples appends " [f32]" when the kernel read them
+ * itself and " [f32 widened]" when the rows were widened into a workspace first; float64
+ * calls report the plain string. Diagnostics/profiling. */
 const char* dfmi_last_demod_kernel(void);
 
 #ifdef __cplusplus
