@@ -1354,6 +1354,17 @@ int ekf_pit_run(int dev, const double* dx, int64_t nrec, int64_t rs, int64_t n, 
   if (hist_n) HIPCHK(hipMemsetAsync(hist, 0xFF, (size_t)nrec * hist_n * 8, st));  // NaN: pass not run
   hipLaunchKernelGGL(dfmi::ekf_pit_head_kernel, dim3((unsigned)((nrec + 3) / 4)), dim3(64), 0, st, dx, nrec, rs, T0,
                      dx0, dp0, dq, dr, wt, (double*)hs, (double*)hst, tk);
+  // Snapshots that fall inside the head (R <= T0) are the sequential kernel's own, written here
+  // and left alone by the passes: while P collapses from P0 the scan's elements are
+  // ill-conditioned and the block-entry states it hands the passes carry ~1e-12 of rounding (a
+  // snapshot at sample 84 of a 4,133-sample record was 1.02e-12 from the C oracle at B = 16,
+  // tests/test_gpu_ekf_matrix.py), which no further pass removes. With R > T0 no snapshot falls
+  // there and nothing is launched.
+  const int64_t k_seq = (nbuf > 0 && (int64_t)R <= T0) ? T0 : 0;
+  if (k_seq > 0) {
+    const char* head_name;
+    if (int rc = ekf_seq_launch(dx, nrec, rs, k_seq, dx0, dp0, dq, dr, wt, R, nbuf, dstates, st, &head_name)) return rc;
+  }
   if (xbar)  // the unfused path: the trajectory buffer too
     hipLaunchKernelGGL(dfmi::ekf_pit_gather_kernel, dim3((unsigned)((slots + 255) / 256), nr), dim3(256), 0, st, dx,
                        rs, n, (const double*)hs, (const double*)hst, T0, B, nb, w_m, f_samp, (double*)xt,
@@ -1469,7 +1480,7 @@ int ekf_pit_run(int dev, const double* dx, int64_t nrec, int64_t rs, int64_t n, 
       hipLaunchKernelGGL(dfmi::ekf_pit_pass_kernel, lanes, dim3(64), 0, st, (const double*)xt, (const double*)wtt, n,
                          B, nb, dx0, dp0, dq, dr, (const double*)lv[cur][0], tops[cur], lv[cur ^ 1][0], (double*)ent,
                          ch, (double*)conv, (unsigned*)done, rule, (double*)hist, (int)R, nbuf,
-                         dstates, tk);
+                         dstates, tk, k_seq);
     } else {
       hipLaunchKernelGGL(dfmi::ekf_pit_aggregate_kernel, lanes, dim3(64), 0, st, (const double*)xt,
                          (const double*)wtt, (const double*)xbar, n, B, nb, dx0, dp0, dq, dr,
@@ -1478,7 +1489,7 @@ int ekf_pit_run(int dev, const double* dx, int64_t nrec, int64_t rs, int64_t n, 
       scan(lv[0]);
       hipLaunchKernelGGL(dfmi::ekf_pit_blocks_kernel, lanes, dim3(64), 0, st, (const double*)xt, (const double*)wtt,
                          (double*)xbar, n, B, nb, dx0, dp0, dq, dr, (const double*)lv[0][0], tops[0],
-                         (const dfmi::PitChan*)ch, (double*)conv, (int)R, nbuf, dstates, rule.measure, tk);
+                         (const dfmi::PitChan*)ch, (double*)conv, (int)R, nbuf, dstates, rule.measure, tk, k_seq);
       hipLaunchKernelGGL(dfmi::ekf_pit_check_kernel, dim3((unsigned)((nrec + 63) / 64)), dim3(64), 0, st,
                          (double*)conv, nrec, rule, ch, (double*)hist);
     }

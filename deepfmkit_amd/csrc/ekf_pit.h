@@ -26,6 +26,11 @@
 //      ekf_pit_aggregate_kernel at the seeded trajectory (ekf_pit_head_kernel); the separate
 //      aggregate / ekf_pit_blocks_kernel pair per pass remains behind the ekf_pit_fused knob.
 //
+// Snapshots up to sample k_seq (the head's length when R <= it, else 0) are not the passes':
+// the sequential kernel writes them once, before the first pass (dfmi_capi.hip ekf_pit_run), and
+// the pass kernels neither write nor measure them. While P collapses from P0 the scan's
+// elements are ill-conditioned and its block-entry states carry ~1e-12 of rounding there.
+//
 // Convergence (pit_decide, on the device: the pass kernel's last workgroup of a channel, or
 // ekf_pit_check_kernel on the unfused path) bounds the distance of the output snapshots from
 // the iteration's fixed point by rho / (1 - rho) d_k <= 1e-13, with d_k their largest relative
@@ -977,7 +982,8 @@ __global__ __launch_bounds__(64) void ekf_pit_blocks_kernel(const double* __rest
                                                             const double* __restrict__ agg,
                                                             const double* __restrict__ tot, const PitChan* __restrict__ ch,
                                                             double* __restrict__ conv, int R, int64_t nbuf,
-                                                            double* __restrict__ states, int measure, DfmiTrigK tk) {
+                                                            double* __restrict__ states, int measure, DfmiTrigK tk,
+                                                            int64_t k_seq) {
   const int64_t r = blockIdx.y;
   if (ch[r].status) return;
   const int64_t b0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1022,7 +1028,7 @@ __global__ __launch_bounds__(64) void ekf_pit_blocks_kernel(const double* __rest
           xbar[(r * 5 + c) * slots + s1] = st[c];
         }
       }
-      if ((k + 1) % R == 0) {
+      if ((k + 1) % R == 0 && k + 1 > k_seq) {  // up to sample k_seq: the sequential head run's snapshots stand
         const int64_t bi = (k + 1) / R - 1;
         if (bi < nbuf) pit_snapshot(states + (r * nbuf + bi) * 5, st, dsnap);
       }
@@ -1062,7 +1068,7 @@ __global__ __launch_bounds__(64) void ekf_pit_pass_kernel(const double* __restri
                                                           PitChan* __restrict__ ch, double* __restrict__ conv,
                                                           unsigned* __restrict__ done, PitRule rule, double* __restrict__ hist, int R,
                                                           int64_t nbuf, double* __restrict__ states,
-                                                          DfmiTrigK tk) {
+                                                          DfmiTrigK tk, int64_t k_seq) {
   const int64_t r = blockIdx.y;
   if (ch[r].status) return;
   const int64_t b0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1124,7 +1130,7 @@ __global__ __launch_bounds__(64) void ekf_pit_pass_kernel(const double* __restri
       for (int c = 0; c < 5; ++c) eps = fma(H[c], xp[c] - bv[c], eps);
       pit_fold(A, bv, C, et, J, Q, Rv, H, eps);
       const int64_t k = b * B + i;
-      if ((k + 1) % R == 0) {
+      if ((k + 1) % R == 0 && k + 1 > k_seq) {  // up to sample k_seq: the sequential head run's snapshots stand
         const int64_t bi = (k + 1) / R - 1;
         if (bi < nbuf) pit_snapshot(states + (r * nbuf + bi) * 5, st, dsnap);
       }
