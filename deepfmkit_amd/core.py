@@ -239,12 +239,19 @@ class DeepFitFramework:
         return n
 
     def fit(self, main_label, method="nls", fit_label=None, **kwargs):
-        """core.py:424-517: strategy dispatch -> DataFrame -> DeepFitObject."""
+        """core.py:424-517: strategy dispatch -> DataFrame -> DeepFitObject.
+
+        errors=True (method 'nls' only): the frame also carries amp_err, m_err, phi_err, psi_err
+        (the standard errors at each buffer's fitted parameters, StandardNLSFitter.fit) and
+        tau_err = m_err / (2 pi df) (zeros without a simulation); the DeepFitObject gets
+        attributes of the same names. Without it the frame and the object are unchanged."""
         _fitters.mark("fit")
         fitter_map = _fitters.FITTER_MAP
         if method not in fitter_map:
             log.error(f"Unknown fit method: '{method}'. Available: {list(fitter_map.keys())}")
             return
+        if kwargs.get("errors") and method != "nls":
+            raise ValueError(f"errors=True is available for method 'nls' only, got '{method}'")
         if main_label not in self.raws:
             log.error(f"Invalid raw data label: '{main_label}' !!")
             return
@@ -284,6 +291,9 @@ class DeepFitFramework:
             # would copy the array in), same columns, order and dtypes
             m = cols["m"]
             cols["tau"] = m / (2 * np.pi * raw.sim.laser.df) if raw.sim else np.zeros(m.shape[0])
+            if "m_err" in cols:  # fit(errors=True): the error of tau, formed as tau is
+                me = cols["m_err"]
+                cols["tau_err"] = me / (2 * np.pi * raw.sim.laser.df) if raw.sim else np.zeros(me.shape[0])
             df = pd.DataFrame(cols, copy=False)
         _fitters.mark("tau")
         self.fits_df[fit_label] = df
@@ -293,6 +303,9 @@ class DeepFitFramework:
         fit.t0, fit.f_samp, fit.f_mod = raw.t0, raw.f_samp, raw.f_mod
         for k in ("ssq", "amp", "m", "tau", "phi", "psi", "dc"):
             setattr(fit, k, cols[k] if k in cols else df[k].to_numpy())
+        if "m_err" in cols:
+            for k in _fitters.ERR_COLUMNS + ["tau_err"]:
+                setattr(fit, k, cols[k])
         _fitters.mark("columns")
         fit.time = _time_axis(fit.ssq.shape[0], fit.fs)
         fit.label = fit_label
@@ -308,7 +321,9 @@ class DeepFitFramework:
         f"{label}_{method}" under which self.fits / self.fits_df store the results; channels
         that share f_samp, f_mod and length go through one engine call. Raises fit()'s
         ValueError when the record length is not a multiple of R (fitters.py:375, 412).
-        Returns {label: DeepFitObject}."""
+        errors=True (method 'nls' only) as in fit(). Returns {label: DeepFitObject}."""
+        if kwargs.get("errors") and method != "nls":
+            raise ValueError(f"errors=True is available for method 'nls' only, got '{method}'")
         raws = [self.raws[l] for l in labels]
         r0 = raws[0]
         if any(r.f_samp != r0.f_samp or r.f_mod != r0.f_mod or r.n_samples() != r0.n_samples() for r in raws):
@@ -332,9 +347,14 @@ class DeepFitFramework:
             raise ValueError(f"cannot reshape array of size {N} into shape ({R})")
         parallel = kwargs.get("parallel", True)
         g = (kwargs.get("init_a", 1.6), kwargs.get("init_m", 6.0), 0.0, kwargs.get("init_psi", 0.0))
-        cols, ok = _fitters.nls_records([r.samples() for r in raws], r0.f_samp, r0.f_mod, R, nbuf, ndata, g,
-                                        parallel=parallel, n_cores=kwargs.get("n_cores") if parallel else None)
-        df_all = _fitters.frame_from(cols, ok)
+        if kwargs.get("errors"):
+            df_all = _fitters.frame_with_errors(*_fitters.nls_records(
+                [r.samples() for r in raws], r0.f_samp, r0.f_mod, R, nbuf, ndata, g, parallel=parallel,
+                n_cores=kwargs.get("n_cores") if parallel else None, errors=True))
+        else:
+            cols, ok = _fitters.nls_records([r.samples() for r in raws], r0.f_samp, r0.f_mod, R, nbuf, ndata, g,
+                                            parallel=parallel, n_cores=kwargs.get("n_cores") if parallel else None)
+            df_all = _fitters.frame_from(cols, ok)
         for i, (l, raw) in enumerate(zip(labels, raws)):
             df = df_all.iloc[i * nbuf:(i + 1) * nbuf].reset_index(drop=True)
             out[l] = self._finish(f"{l}_{method}", l, raw, method, df, n, R, fs, nbuf)  # fit()'s default label

@@ -34,6 +34,8 @@
 namespace dfmi {
 hipError_t snr_gen_launch(const dfmi_snr_params& p, int64_t idx0, int64_t n, double* out, int n_cu, hipStream_t st);
 hipError_t bessel_eval_launch(const double* x, int64_t nx, int nmax, int method, double* out, hipStream_t st);
+hipError_t fisher_launch(const double* params, int64_t n, int64_t ld, int ndata, const double* var, double var_mul,
+                         double* jtj, double* cov, double* sigma, int32_t* ok, hipStream_t st);
 }
 
 namespace {
@@ -2194,6 +2196,44 @@ int dfmi_bessel_eval(const double* x, int64_t nx, int32_t nmax, int32_t method, 
     HIPCHK(hipMemcpyAsync(out, dout, ob, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
   }
+  return DFMI_OK;
+}
+
+int dfmi_fisher(const double* params, int64_t n, int64_t ld, int32_t ndata, const double* var, double var_mul,
+                double* jtj, double* cov, double* sigma, int32_t* ok, int32_t mem, void* stream) {
+  CallScope cs(stream);
+  if (n < 0 || ld < n || ndata <= 0) return fail(DFMI_ERR_ARG, "bad fisher geometry (n >= 0, ld >= n, ndata > 0)");
+  if (!jtj && !cov && !sigma) return fail(DFMI_ERR_ARG, "fisher: one of jtj, cov, sigma is required");
+  if (n > 0 && !params) return fail(DFMI_ERR_ARG, "null pointer");
+  int dev;
+  int rc = ensure_init(&dev);
+  if (rc) return rc;
+  if (n == 0) return DFMI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  if (mem == DFMI_MEM_DEVICE) {
+    HIPCHK(dfmi::fisher_launch(params, n, ld, ndata, var, var_mul, jtj, cov, sigma, ok, st));
+    return DFMI_OK;
+  }
+  // host memory: the four parameter rows (and var) packed with ld = n, the outputs behind them
+  void *din, *dout, *dok;
+  const size_t rb = (size_t)n * 8;
+  if ((rc = workspace(dev, "f_in", 5 * rb, &din))) return rc;
+  if ((rc = workspace(dev, "f_out", 24 * rb, &dout))) return rc;
+  if ((rc = workspace(dev, "f_ok", (size_t)n * 4, &dok))) return rc;
+  double* dp = (double*)din;
+  for (int i = 0; i < 4; ++i)
+    HIPCHK(hipMemcpyAsync(dp + (size_t)i * n, params + (size_t)i * ld, rb, hipMemcpyHostToDevice, st));
+  if (var) HIPCHK(hipMemcpyAsync(dp + (size_t)4 * n, var, rb, hipMemcpyHostToDevice, st));
+  double* dj = (double*)dout;
+  double* dc = dj + (size_t)10 * n;
+  double* dsg = dj + (size_t)20 * n;
+  HIPCHK(dfmi::fisher_launch(dp, n, n, ndata, var ? dp + (size_t)4 * n : nullptr, var_mul, jtj ? dj : nullptr,
+                             cov ? dc : nullptr, sigma ? dsg : nullptr, ok ? (int32_t*)dok : nullptr, st));
+  if (jtj) HIPCHK(hipMemcpyAsync(jtj, dj, 10 * rb, hipMemcpyDeviceToHost, st));
+  if (cov) HIPCHK(hipMemcpyAsync(cov, dc, 10 * rb, hipMemcpyDeviceToHost, st));
+  if (sigma) HIPCHK(hipMemcpyAsync(sigma, dsg, 4 * rb, hipMemcpyDeviceToHost, st));
+  if (ok) HIPCHK(hipMemcpyAsync(ok, dok, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
   return DFMI_OK;
 }
 

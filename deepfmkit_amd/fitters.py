@@ -35,6 +35,7 @@ from . import fit as _fit
 log = logging.getLogger(__name__)
 
 COLUMNS = ["amp", "m", "phi", "psi", "dc", "ssq", "fitok"]
+ERR_COLUMNS = ["amp_err", "m_err", "phi_err", "psi_err"]  # fit(errors=True): appended after fitok
 
 # Facade timing marks (scripts/profile_facade.py sets a list here): (label, perf_counter())
 # appended at each stage of DeepFitFramework.fit's NLS path; None = off (one test per mark).
@@ -85,8 +86,31 @@ def w0_of(f_mod, f_samp):
     return 2.0 * np.pi * f_mod / f_samp
 
 
+def _check_errors_ndata(ndata):
+    """errors=True needs degrees of freedom: 2*ndata residuals, 4 parameters."""
+    if ndata < 3:
+        raise ValueError(f"errors=True needs ndata >= 3 (2*ndata - 4 degrees of freedom), got ndata={ndata}")
+
+
+def _segment_errors(lib, out, nseg, ndata, mem, stream):
+    """Standard errors (4, nseg) of the fits in `out` (nls_records' result block: rows 0-3 the
+    parameters, row 5 ssq, leading dimension nseg): sqrt(diag(ssq/(2 ndata - 4) (J^T J)^-1)) by
+    ONE dfmi_fisher call reading the block in place — on `stream`, straight behind the record
+    call, for a device block."""
+    if mem == _lib.DFMI_MEM_DEVICE:
+        import torch
+        sig = torch.empty((4, nseg), dtype=torch.float64, device=out.device)
+    else:
+        sig = np.empty((4, nseg))
+    base = _lib.ptr(out)
+    rc = lib.dfmi_fisher(base, nseg, nseg, ndata, base + 5 * nseg * 8, 1.0 / (2 * ndata - 4), None, None,
+                         _lib.ptr(sig), None, mem, stream)
+    _lib.check(rc, "dfmi_fisher")
+    return sig
+
+
 def nls_records(records, f_samp, f_mod, R, nbuf, ndata=10, init_guess=(1.6, 6.0, 0.0, 0.0), parallel=True,
-                n_cores=None):
+                n_cores=None, errors=False):
     """Run the StandardNLSFitter pipeline on one or more equal-length records in ONE
     GPU call (config 3: several channels as one batch).
 
@@ -95,7 +119,11 @@ def nls_records(records, f_samp, f_mod, R, nbuf, ndata=10, init_guess=(1.6, 6.0,
     on load: the same bits as for the widened record); host arrays of any other dtype are widened
     to float64, device tensors of any other dtype are refused. init_guess: (4,) shared or
     (nrec, 4). Returns (cols (6, nrec*nbuf) in the order amp, m, phi, psi, dc, ssq; fitok
-    (nrec*nbuf,)), as numpy arrays for host input and as CUDA tensors for device input."""
+    (nrec*nbuf,)), as numpy arrays for host input and as CUDA tensors for device input.
+    errors=True: a third value, the (4, nrec*nbuf) standard errors of amp, m, phi, psi
+    (_segment_errors; NaN where J^T J at the fitted point has no inverse); ndata >= 3."""
+    if errors:
+        _check_errors_ndata(ndata)
     lib = _lib.load()
     w0 = w0_of(f_mod, f_samp)
     if isinstance(records, (list, tuple)):
@@ -140,6 +168,10 @@ def nls_records(records, f_samp, f_mod, R, nbuf, ndata=10, init_guess=(1.6, 6.0,
                                                _torch_stream(x.device))
         _lib.check(rc, "dfmi_nls_record")
         mark("enqueue")
+        if errors:
+            with _on_device(x):
+                sig = _segment_errors(lib, out, nseg, ndata, _lib.DFMI_MEM_DEVICE, _torch_stream(x.device))
+            return out, ok, sig
         return out, ok
     out = np.empty((6, nseg))
     ok = np.empty(nseg, dtype=np.int32)
@@ -152,10 +184,13 @@ def nls_records(records, f_samp, f_mod, R, nbuf, ndata=10, init_guess=(1.6, 6.0,
                                  1 if parallel else 0, max(nchunk, 1), cfg, _lib.ptr(out), _lib.ptr(ok),
                                  _lib.DFMI_MEM_HOST, None)
     _lib.check(rc, "dfmi_nls_record")
+    if errors:
+        return out, ok, _segment_errors(lib, out, nseg, ndata, _lib.DFMI_MEM_HOST, None)
     return out, ok
 
 
-def nls_record_devices(x, f_samp, f_mod, R, nbuf, devices, ndata=10, init_guess=(1.6, 6.0, 0.0, 0.0)):
+def nls_record_devices(x, f_samp, f_mod, R, nbuf, devices, ndata=10, init_guess=(1.6, 6.0, 0.0, 0.0),
+                       errors=False):
     """One record's _fit_parallel with chunk size 1 (fitters.py:395-428: buffer 0 fitted from
     init_guess, every other buffer seeded with its result) spread over several GPUs of this
     process: buffers 1..nbuf-1 are cut into len(devices) contiguous shards (np.array_split),
@@ -167,7 +202,11 @@ def nls_record_devices(x, f_samp, f_mod, R, nbuf, devices, ndata=10, init_guess=
     samples); the shards are allocated in the record's dtype.
     Returns (cols (6, nbuf) numpy in the order amp, m, phi, psi, dc, ssq; fitok (nbuf,)),
     bit-identical to one nls_records call (segments are independent once the seed is known).
-    Same-device entries are allowed (shards then run one after another on that GPU)."""
+    Same-device entries are allowed (shards then run one after another on that GPU).
+    errors=True: each shard's standard errors are formed on its device (nls_records) and a third
+    value, (4, nbuf) numpy, is returned."""
+    if errors:
+        _check_errors_ndata(ndata)
     import torch
     devs = [torch.device("cuda", int(d)) if not isinstance(d, torch.device) else d for d in devices]
     if not devs:
@@ -195,18 +234,24 @@ def nls_record_devices(x, f_samp, f_mod, R, nbuf, devices, ndata=10, init_guess=
                 xs[:R].copy_(x[:R])
                 if b1 > b0:
                     xs[R:].copy_(x[b0 * R:b1 * R])
-            cols, ok = nls_records(xs.view(1, -1), f_samp, f_mod, R, n_s, ndata, init_guess, parallel=True)
-        pending.append((cols, ok, b1 > b0))
-    out_cols, out_ok = [], []
-    for k, (cols, ok, has_rows) in enumerate(pending):
+            res = nls_records(xs.view(1, -1), f_samp, f_mod, R, n_s, ndata, init_guess, parallel=True,
+                              errors=errors)
+        pending.append((res[0], res[1], b1 > b0, res[2] if errors else None))
+    out_cols, out_ok, out_sig = [], [], []
+    for k, (cols, ok, has_rows, sig) in enumerate(pending):
         c = cols.cpu().numpy()
         o = ok.cpu().numpy()
+        g = sig.cpu().numpy() if errors else None
         if k == 0:
             out_cols.append(c)
             out_ok.append(o)
+            out_sig.append(g)
         elif has_rows:
             out_cols.append(c[:, 1:])
             out_ok.append(o[1:])
+            out_sig.append(g[:, 1:] if errors else None)
+    if errors:
+        return np.concatenate(out_cols, axis=1), np.concatenate(out_ok), np.concatenate(out_sig, axis=1)
     return np.concatenate(out_cols, axis=1), np.concatenate(out_ok)
 
 
@@ -290,6 +335,17 @@ def frame_from(cols, fitok, tau_div=NO_TAU):
     return df
 
 
+def frame_with_errors(cols, fitok, sig):
+    """frame_from's frame with the float64 columns amp_err, m_err, phi_err, psi_err appended
+    after fitok (fit(errors=True)); the seven base columns are frame_from's own arrays."""
+    df = frame_from(cols, fitok)  # kept alive: frame_arrays answers for a living frame only
+    base = frame_arrays(df)[0]
+    if hasattr(sig, "cpu"):
+        sig = sig.cpu().numpy()
+    sig = np.ascontiguousarray(sig, dtype=np.float64)
+    return pd.DataFrame({**base, **{k: sig[i] for i, k in enumerate(ERR_COLUMNS)}}, copy=False)
+
+
 class BaseFitter(ABC):
     """fitters.py:164-208."""
 
@@ -313,7 +369,10 @@ class StandardNLSFitter(BaseFitter):
     is its own chunk (the GPU-natural split; the reference's own chunk choice
     changes results by <= 2.5e-10), with n_cores=k the buffers are
     split into k warm-start chains exactly as np.array_split does.
-    parallel=False follows _fit_sequential (one warm-start chain)."""
+    parallel=False follows _fit_sequential (one warm-start chain).
+    errors=True appends the float64 columns amp_err, m_err, phi_err, psi_err after fitok: the
+    standard errors sqrt(diag(ssq/(2 ndata - 4) (J^T J)^-1)) at each buffer's fitted parameters
+    (dfmi_fisher on the device, behind the fit; needs ndata >= 3)."""
 
     def fit(self, main_raw, **kwargs) -> pd.DataFrame:
         n = self.config["n"]
@@ -322,6 +381,9 @@ class StandardNLSFitter(BaseFitter):
         init_a = kwargs.get("init_a", 1.6)
         init_m = kwargs.get("init_m", 6.0)
         init_psi = kwargs.get("init_psi", 0.0)
+        errors = bool(kwargs.get("errors", False))
+        if errors:
+            _check_errors_ndata(ndata)
         R, _, nbuf = _calculate_fit_params(main_raw, n)
         if nbuf == 0:
             return pd.DataFrame()
@@ -339,6 +401,14 @@ class StandardNLSFitter(BaseFitter):
             raise ValueError("devices= applies to parallel=True without n_cores (chunk size 1); "
                              f"got parallel={parallel}, n_cores={kwargs.get('n_cores')}")
         mark("fitter_args")
+        if errors:
+            g = (init_a, init_m, 0.0, init_psi)
+            if devices is not None:
+                res = nls_record_devices(x, main_raw.f_samp, main_raw.f_mod, R, nbuf, devices, ndata, g, errors=True)
+            else:
+                res = nls_records(x.reshape(1, N), main_raw.f_samp, main_raw.f_mod, R, nbuf, ndata, g,
+                                  parallel=parallel, n_cores=kwargs.get("n_cores") if parallel else None, errors=True)
+            return frame_with_errors(*res)
         if devices is not None:
             cols, ok = nls_record_devices(x, main_raw.f_samp, main_raw.f_mod, R, nbuf, devices, ndata,
                                           (init_a, init_m, 0.0, init_psi))

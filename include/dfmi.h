@@ -37,6 +37,9 @@
  *                    trial, the input side of workers.run_efficiency_trial batches
  *   dfmi_wdfmi_fit   WDFMI_NLSFitter / WDFMI_OrthogonalFitter / WDFMI_SequentialFitter /
  *                    HWDFMI_Fitter .fit (fitters.py:481-891)
+ *   dfmi_fisher      the J^T J of coeffs (fit.py:68-150) and its inverse at caller points:
+ *                    calculate_crlb_for_m / calculate_m_precision (helpers.py:16-45, 98-132),
+ *                    and the per-segment standard errors of a fit (no reference counterpart)
  */
 #ifndef DFMI_H
 #define DFMI_H
@@ -284,6 +287,27 @@ int dfmi_synth_snr(const dfmi_snr_params* prm, int64_t idx0, int64_t n, double* 
  * 2: the register path of ndata <= 16 (nmax <= 17). */
 int dfmi_bessel_eval(const double* x, int64_t nx, int32_t nmax, int32_t method, double* out, int32_t mem,
                      void* stream);
+
+/* Fisher matrix, parameter covariance and standard errors of the DFMI model at n points.
+ * The model Jacobian J (2*ndata x 4, fit.py:68-150) depends on (amp, m, phi, psi) alone.
+ *   params[i*ld + s], i < 4, ld >= n     input amp, m, phi, psi of point s: the layout of
+ *                                        dfmi_lm's params and of rows 0-3 of dfmi_nls_record's
+ *                                        out (pass out itself, var = out + 5*ld: the ssq row,
+ *                                        var_mul = 1/(2*ndata - 4))
+ *   var[s] * var_mul                     the variance factor of point s; var == NULL: var_mul
+ *   jtj[k*n + s], k < 10                 J^T J, upper triangle 00 01 02 03 11 12 13 22 23 33
+ *   cov[k*n + s], k < 10                 var * (J^T J)^-1, same order
+ *   sigma[i*n + s], i < 4                sqrt(cov_ii)
+ *   ok[s]                                1, or 0 where J^T J has no inverse (a parameter, the
+ *                                        variance or a diagonal entry non-finite, the variance
+ *                                        negative, a diagonal entry or a pivot of the
+ *                                        factorisation <= 0, e.g. amp = 0 or m = 0): cov and
+ *                                        sigma are NaN there and only there, jtj is what was
+ *                                        computed
+ * Any of jtj, cov, sigma, ok may be NULL (not written), but not all of jtj, cov, sigma.
+ * ndata: any value dfmi_lm's general path takes (ndata > 0). n == 0 launches nothing. */
+int dfmi_fisher(const double* params, int64_t n, int64_t ld, int32_t ndata, const double* var, double var_mul,
+                double* jtj, double* cov, double* sigma, int32_t* ok, int32_t mem, void* stream);
 
 /* ---- Witness-based fitters (EXPERIMENTAL in the reference) ----
  * Replace, per record (main channel + witness channel):
