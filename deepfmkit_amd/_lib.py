@@ -31,7 +31,7 @@ SYMBOLS = ("dfmi_lm_config_default", "dfmi_demod", "dfmi_lm", "dfmi_nls_record",
            "dfmi_record_moments", "dfmi_synth_asd", "dfmi_synth_snr", "dfmi_bessel_eval",
            "dfmi_release_workspaces", "dfmi_step_timing", "dfmi_step_timing_read", "dfmi_ekf_pit_passes",
            "dfmi_ekf_pit_trace", "dfmi_demod_typed", "dfmi_demod_rows_typed", "dfmi_nls_record_typed",
-           "dfmi_fisher")
+           "dfmi_fisher", "dfmi_lpsd_plan", "dfmi_lpsd")
 
 
 class DFMIError(RuntimeError):
@@ -228,6 +228,10 @@ def load():
         lib.dfmi_bessel_eval.restype = ctypes.c_int
         lib.dfmi_fisher.argtypes = [P, i64, i64, i32, P, dbl, P, P, P, P, i32, P]
         lib.dfmi_fisher.restype = ctypes.c_int
+        lib.dfmi_lpsd_plan.argtypes = [i64, dbl, dbl, dbl, i64, i64, i64, P, P, P, P, P, i64]
+        lib.dfmi_lpsd_plan.restype = i64
+        lib.dfmi_lpsd.argtypes = [P, i64, i64, i64, dbl, P, P, P, i64, i32, dbl, P, P, i32, P]
+        lib.dfmi_lpsd.restype = ctypes.c_int
         lib.dfmi_wdfmi_fit.argtypes = [P, i64, i64, i64, i32, P, i64, ctypes.POINTER(WdfmiConfig), P, P, i32, P]
         lib.dfmi_wdfmi_fit.restype = ctypes.c_int
         lib.dfmi_detect_period.argtypes = [dbl, i32, i32]

@@ -5,9 +5,10 @@ for zero/white noise), new_sim / load_sim, create_witness_channel, fit_init,
 fit (strategy dispatch, tau column, DeepFitObject), fit_many — several
 equal-length channels fitted as ONE GPU batch (config 3) — and the text formats:
 parse_header, load_raw, load_fit, to_txt (core.py:119-174, 259-332; parsed and
-written by libdfmi's host code, deepfmkit_amd/textio.py).
+written by libdfmi's host code, deepfmkit_amd/textio.py), and calc_lpsd
+(core.py:590-609; deepfmkit_amd/lpsd.py).
 
-Out of scope (SURVEY.md §2 "OUT"): LPSD, plotting.
+Out of scope (SURVEY.md §2 "OUT"): plotting.
 """
 from __future__ import annotations
 
@@ -359,3 +360,30 @@ class DeepFitFramework:
             df = df_all.iloc[i * nbuf:(i + 1) * nbuf].reset_index(drop=True)
             out[l] = self._finish(f"{l}_{method}", l, raw, method, df, n, R, fs, nbuf)  # fit()'s default label
         return out
+
+    # --- spectra (core.py:590-609) ------------------------------------------------
+    def calc_lpsd(self, labels=None, which="phi"):
+        """LPSD of the fitted `which` ('phi' in the reference) of the fits under `labels`, or of
+        all fits: sets each fit's f and Sxx. Fits of equal length, data rate and LPSD settings
+        share one GPU call (they share the plan and the windows). A label without a fit logs
+        the reference's warning and changes nothing."""
+        from .lpsd import lpsd
+        groups = {}
+        for label in (self.fits if labels is None else labels):
+            try:
+                fit = self.fits[label]
+                x = np.asarray(getattr(fit, which), dtype=np.float64).reshape(-1)
+                st = fit.lpsd_settings()
+                key = (x.size, float(fit.fs)) + tuple(st[k] if k != "win" else id(st[k]) for k in sorted(st))
+            except (KeyError, TypeError, AttributeError):
+                log.warning("Specified label is invalid!")
+                continue
+            groups.setdefault(key, []).append((fit, x, st))
+        for members in groups.values():
+            fits = []  # a label named twice is computed once
+            for m in members:
+                if all(m[0] is not o[0] for o in fits):
+                    fits.append(m)
+            r = lpsd(np.stack([x for _, x, _ in fits]), fits[0][0].fs, **fits[0][2])
+            for i, (fit, _, _) in enumerate(fits):
+                fit.f, fit.Sxx = r.f.copy(), np.ascontiguousarray(r.Sxx[i])

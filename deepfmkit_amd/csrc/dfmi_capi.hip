@@ -9,7 +9,9 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <algorithm>
 #include <array>
+#include <cmath>
 #include <cstdint>
 #include <map>
 #include <mutex>
@@ -30,8 +32,14 @@
 #include "moments.h"
 #include "synth.h"
 #include "wdfmi.h"
+#include "lpsd.h"
 
 namespace dfmi {
+hipError_t lpsd_batch_launch(const double* x, int64_t nser, int64_t ser_stride, int64_t N, double fs,
+                             const LpsdFreq* fr, int nf, int n256, int64_t maxL, int64_t tiles256, int64_t tiles64,
+                             int order, double pa, double inv_i0, const double* rk2, int64_t woff0, double* win,
+                             double* wsum, int64_t toff0, int64_t tiles_ld, double* tile, int64_t J, double* Sxx,
+                             double* enbw, hipStream_t st);
 hipError_t snr_gen_launch(const dfmi_snr_params& p, int64_t idx0, int64_t n, double* out, int n_cu, hipStream_t st);
 hipError_t bessel_eval_launch(const double* x, int64_t nx, int nmax, int method, double* out, hipStream_t st);
 hipError_t fisher_launch(const double* params, int64_t n, int64_t ld, int ndata, const double* var, double var_mul,
@@ -117,6 +125,8 @@ struct Tuning {
   int ekf_pit_measure = 0;    // the stop rule's move: 0 the output snapshots, 1 (diagnostics) the block entries
   int ekf_pit_head = 256;     // samples the sequential EKF runs first to seed the trajectory (ekf_pit_head_kernel)
   int ekf_pit_fused = 1;      // 1: EKF + fold in one kernel per pass (ekf_pit_pass_kernel); 0: separate kernels
+  int lpsd_batch_mb = 512;    // dfmi_lpsd: MiB of window + tile workspace per batch of frequencies (a batch holds
+                              // at least one frequency; 0 = one frequency per batch); same bits
 };
 Tuning g_tune;
 
@@ -1203,7 +1213,8 @@ const std::map<std::string, Knob>& knobs() {
       {"ekf_pit_seq", {&Tuning::ekf_pit_seq, {0, 1}}},
       {"ekf_pit_measure", {&Tuning::ekf_pit_measure, {0, 1}}},
       {"ekf_pit_head", {&Tuning::ekf_pit_head, {}}},
-      {"ekf_pit_fused", {&Tuning::ekf_pit_fused, {0, 1}}}};
+      {"ekf_pit_fused", {&Tuning::ekf_pit_fused, {0, 1}}},
+      {"lpsd_batch_mb", {&Tuning::lpsd_batch_mb, {}}}};
   return k;
 }
 // np.mean / np.var of nrec device records on st (moments.hip), numpy-exact.
@@ -2234,6 +2245,112 @@ int dfmi_fisher(const double* params, int64_t n, int64_t ld, int32_t ndata, cons
   if (sigma) HIPCHK(hipMemcpyAsync(sigma, dsg, 4 * rb, hipMemcpyDeviceToHost, st));
   if (ok) HIPCHK(hipMemcpyAsync(ok, dok, (size_t)n * 4, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
+  return DFMI_OK;
+}
+
+// dfmi_lpsd's window and tile workspaces together stay within lpsd_batch_mb (tuning key,
+// default 512 MiB) per batch of frequencies; a batch always holds at least one frequency
+// (one frequency's window is at most N doubles and its tiles nser x K).
+constexpr int kLpsdBatchFreqs = 32768;
+
+int dfmi_lpsd(const double* x, int64_t nser, int64_t ser_stride, int64_t N, double fs, const double* b,
+              const int64_t* L, const int64_t* K, int64_t J, int32_t order, double psll, double* Sxx, double* enbw,
+              int32_t mem, void* stream) {
+  CallScope cs(stream);
+  if (nser < 1 || nser > 65535 || N < 1 || N > INT32_MAX || J < 1 || J > INT32_MAX)
+    return fail(DFMI_ERR_ARG, "bad lpsd geometry (1 <= nser <= 65535, 1 <= N < 2^31, J >= 1)");
+  if (nser > 1 && ser_stride < N) return fail(DFMI_ERR_ARG, "ser_stride < N");
+  if (!(fs > 0.0) || !std::isfinite(fs)) return fail(DFMI_ERR_ARG, "lpsd: fs must be positive and finite");
+  if (order != 0 && order != -1) return fail(DFMI_ERR_ARG, "lpsd: order must be 0 (segment mean removed) or -1 (nothing)");
+  if (!x || !b || !L || !K || !Sxx || !enbw) return fail(DFMI_ERR_ARG, "null pointer");
+  const double pa = dfmi::kLpsdPi * dfmi::lpsd_kaiser_alpha(psll);
+  if (!(pa > 0.0 && pa <= dfmi::kLpsdI0Max))
+    return fail(DFMI_ERR_ARG, "lpsd: psll outside the Kaiser fit's range (0 < pi alpha(psll) <= 64)");
+  for (int64_t j = 0; j < J; ++j)
+    if (L[j] < 1 || L[j] > N || K[j] < 1 || K[j] > INT32_MAX || !(b[j] >= 0.0) || !std::isfinite(b[j]))
+      return fail(DFMI_ERR_ARG, "lpsd: a plan entry is outside 1 <= L <= N, K >= 1, b >= 0");
+  int dev;
+  int rc = ensure_init(&dev);
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+
+  // frequencies sorted longest segment first (stable), window rows and tile slots in that order
+  std::vector<int64_t> ord((size_t)J);
+  for (int64_t j = 0; j < J; ++j) ord[(size_t)j] = j;
+  std::stable_sort(ord.begin(), ord.end(), [&](int64_t a, int64_t c) { return L[a] > L[c]; });
+  // one upload: the frequency table, then the 1/k^2 table of lpsd_i0
+  std::vector<double> up((size_t)J * (sizeof(dfmi::LpsdFreq) / 8) + dfmi::kLpsdI0Terms);
+  dfmi::LpsdFreq* hf = (dfmi::LpsdFreq*)up.data();
+  double* hrk2 = up.data() + (size_t)J * (sizeof(dfmi::LpsdFreq) / 8);
+  dfmi::lpsd_fill_rk2(hrk2);
+  const double inv_i0 = 1.0 / dfmi::lpsd_i0(pa, hrk2);
+  int64_t woff = 0, toff = 0;
+  for (int64_t p = 0; p < J; ++p) {
+    const int64_t j = ord[(size_t)p];
+    hf[p] = dfmi::LpsdFreq{b[j], L[j], K[j], woff, toff, j};
+    woff += L[j];
+    toff += K[j];
+  }
+  // batches of consecutive frequencies within the workspace bound
+  const size_t kLpsdBatchBytes = (size_t)t_tune.lpsd_batch_mb << 20;
+  struct Batch { int64_t p0, p1, nw, nt; };
+  std::vector<Batch> batches;
+  size_t max_w = 0, max_t = 0, max_f = 0;
+  for (int64_t p = 0; p < J;) {
+    Batch bt{p, p, 0, 0};
+    while (bt.p1 < J && bt.p1 - bt.p0 < kLpsdBatchFreqs) {
+      const int64_t nw = bt.nw + hf[bt.p1].L, nt = bt.nt + hf[bt.p1].K;
+      if (bt.p1 > bt.p0 && ((size_t)nw + (size_t)nt * (size_t)nser) * 8 > kLpsdBatchBytes) break;
+      bt.nw = nw;
+      bt.nt = nt;
+      ++bt.p1;
+    }
+    if ((size_t)bt.nt > ((size_t)1 << 30)) return fail(DFMI_ERR_UNSUPPORTED, "lpsd: more than 2^30 segments at one frequency");
+    max_w = std::max(max_w, (size_t)bt.nw);
+    max_t = std::max(max_t, (size_t)bt.nt);
+    max_f = std::max(max_f, (size_t)(bt.p1 - bt.p0));
+    batches.push_back(bt);
+    p = bt.p1;
+  }
+  void *dtab, *dwin, *dtile, *dwsum;
+  if ((rc = workspace(dev, "p_tab", up.size() * 8, &dtab))) return rc;
+  if ((rc = workspace(dev, "p_win", max_w * 8, &dwin))) return rc;
+  if ((rc = workspace(dev, "p_tile", max_t * (size_t)nser * 8, &dtile))) return rc;
+  if ((rc = workspace(dev, "p_wsum", max_f * 16, &dwsum))) return rc;
+  const double* dx = x;
+  double *ds = Sxx, *de = enbw;
+  const int64_t stride = nser > 1 ? ser_stride : N;
+  if (mem != DFMI_MEM_DEVICE) {
+    void *a, *o;
+    if ((rc = workspace(dev, "p_x", (size_t)nser * (size_t)N * 8, &a))) return rc;
+    if ((rc = workspace(dev, "p_out", ((size_t)nser + 1) * (size_t)J * 8, &o))) return rc;
+    for (int64_t r = 0; r < nser; ++r)
+      HIPCHK(hipMemcpyAsync((double*)a + (size_t)r * N, x + (size_t)r * stride, (size_t)N * 8, hipMemcpyHostToDevice, st));
+    dx = (const double*)a;
+    ds = (double*)o;
+    de = ds + (size_t)nser * J;
+  }
+  // the tables are this call's own host memory: uploaded before the call returns
+  HIPCHK(hipMemcpyAsync(dtab, up.data(), up.size() * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(hipStreamSynchronize(st));
+  const dfmi::LpsdFreq* df = (const dfmi::LpsdFreq*)dtab;
+  const double* drk2 = (const double*)dtab + (size_t)J * (sizeof(dfmi::LpsdFreq) / 8);
+  for (const Batch& bt : batches) {
+    int n256 = 0;
+    int64_t t256 = 0;
+    for (int64_t p = bt.p0; p < bt.p1 && hf[p].L > dfmi::kLpsdWaveL; ++p) {
+      ++n256;
+      t256 += hf[p].K;
+    }
+    HIPCHK(dfmi::lpsd_batch_launch(dx, nser, mem != DFMI_MEM_DEVICE ? N : stride, N, fs, df + bt.p0, (int)(bt.p1 - bt.p0),
+                                   n256, hf[bt.p0].L, t256, bt.nt - t256, order, pa, inv_i0, drk2, hf[bt.p0].woff,
+                                   (double*)dwin, (double*)dwsum, hf[bt.p0].toff, bt.nt, (double*)dtile, J, ds, de, st));
+  }
+  if (mem != DFMI_MEM_DEVICE) {
+    HIPCHK(hipMemcpyAsync(Sxx, ds, (size_t)nser * J * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(enbw, de, (size_t)J * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+  }
   return DFMI_OK;
 }
 

@@ -50,7 +50,20 @@ class DeepRawObject:
 
 
 class DeepFitObject:
-    """Fit results of one channel (reference data.py:121-208)."""
+    """Fit results of one channel (reference data.py:121-208, 239-244)."""
+
+    # LPSD results and settings (reference data.py:147-156). Class-level defaults: an
+    # instance carries its own only once calc_lpsd ran or the user set one.
+    f = None
+    Sxx = None
+    olap = "default"
+    bmin = 1
+    Lmin = 0
+    Jdes = 500
+    Kdes = 100
+    order = 0
+    win = staticmethod(np.kaiser)
+    psll = 200
 
     def __init__(self):
         self.fit_file = None
@@ -79,3 +92,16 @@ class DeepFitObject:
         host writer in the reference's exact bytes (textio.write_fit)."""
         from . import textio
         textio.write_fit(self, filename)
+
+    def lpsd_settings(self):
+        """The LPSD settings of this fit as keyword arguments of deepfmkit_amd.lpsd.lpsd."""
+        return dict(olap=self.olap, bmin=self.bmin, Lmin=self.Lmin, Jdes=self.Jdes, Kdes=self.Kdes, order=self.order,
+                    win=self.win, psll=self.psll)
+
+    def calc_lpsd(self, which="phi"):
+        """LPSD of a fitted parameter (the reference's calc_lpsd takes phi, data.py:239-244) at
+        the fit data rate fs with this object's settings: sets f and Sxx, on the GPU
+        (deepfmkit_amd.lpsd; the estimator is the project's own definition)."""
+        from .lpsd import lpsd
+        r = lpsd(np.asarray(getattr(self, which), dtype=np.float64), self.fs, **self.lpsd_settings())
+        self.f, self.Sxx = r.f, r.Sxx

@@ -40,6 +40,8 @@
  *   dfmi_fisher      the J^T J of coeffs (fit.py:68-150) and its inverse at caller points:
  *                    calculate_crlb_for_m / calculate_m_precision (helpers.py:16-45, 98-132),
  *                    and the per-segment standard errors of a fit (no reference counterpart)
+ *   dfmi_lpsd_plan,  DeepFitObject.calc_lpsd / DeepFitFramework.calc_lpsd (data.py:239-244,
+ *   dfmi_lpsd        core.py:590-609), with this project's own definition of the estimator
  */
 #ifndef DFMI_H
 #define DFMI_H
@@ -309,6 +311,42 @@ int dfmi_bessel_eval(const double* x, int64_t nx, int32_t nmax, int32_t method, 
 int dfmi_fisher(const double* params, int64_t n, int64_t ld, int32_t ndata, const double* var, double var_mul,
                 double* jtj, double* cov, double* sigma, int32_t* ok, int32_t mem, void* stream);
 
+/* ---- Log-frequency spectral density (LPSD) of a series ----
+ * The one-sided power spectral density at logarithmically spaced frequencies, one DFT bin per
+ * frequency over overlapped, Kaiser-windowed segments whose length follows the frequency
+ * (Troebs & Heinzel 2006; the definition, this project's own, is DESIGN.md section 13; the
+ * reference calls spectools.lpsd at data.py:239-244 and core.py:590-609).
+ *
+ * dfmi_lpsd_plan: host only, all arithmetic double. For a series of N >= 8 samples at rate
+ * fs > 0, overlap 0 <= olap < 1, bmin > 0, Jdes >= 1, Kdes >= 1 it emits per frequency
+ * f, fres = fs/L, the fractional bin b = f/fres >= bmin, the segment length L and the segment
+ * count K (where rounding L would leave b < bmin, L is the shortest length that keeps it).
+ * Returns J, the number of frequencies (below Jdes), or DFMI_ERR_ARG. With all five outputs
+ * NULL it only counts (call it twice, as dfmi_txt_shape / dfmi_txt_read); otherwise all five
+ * are required with room for cap >= J entries. It sets no dfmi_last_error message. */
+int64_t dfmi_lpsd_plan(int64_t N, double fs, double olap, double bmin, int64_t Lmin, int64_t Jdes, int64_t Kdes,
+                       double* f, double* fres, double* b, int64_t* L, int64_t* K, int64_t cap);
+
+/* dfmi_lpsd: Sxx[r*J + j] for nser series x[r*ser_stride .. + N] of equal length (1 <= N < 2^31,
+ * nser <= 65535) that share the plan (b, L, K)[0..J): always HOST arrays, 1 <= L <= N, K >= 1.
+ *   w[n] = I0(pi alpha sqrt(1 - z^2)) / I0(pi alpha), z = 2n/L - 1 (DFT-even Kaiser),
+ *          alpha from psll by the polynomial of DESIGN.md section 13, 0 < pi alpha <= 64
+ *   segment k starts at floor(k (N-L)/(K-1) + 0.5) (0 when K = 1)
+ *   order 0: the segment's own mean is subtracted before windowing; order -1: nothing
+ *   A = sum_n w[n] (x[s+n] - mean) exp(-2 pi i b n / L)
+ *   Sxx = 2 mean_k |A|^2 / (fs sum w^2),   enbw[j] = fs sum w^2 / (sum w)^2
+ * NaN samples propagate into the frequencies whose segments hold them; that is no error.
+ * x, Sxx (nser x J) and enbw (J) are host or device memory by `mem`; on DFMI_MEM_DEVICE the
+ * kernels are enqueued on `stream` and not waited for (the plan tables are uploaded before
+ * the call returns). Sums have a fixed order: results are bit-identical from run to run, and
+ * a series gives the same bits alone or in a batch. The windows of all frequencies and the
+ * per-segment |A|^2 live in the library's workspaces (dfmi_release_workspaces), at most
+ * 512 MiB together per batch of frequencies (tuning key "lpsd_batch_mb"), or one frequency's
+ * own need if that is more. */
+int dfmi_lpsd(const double* x, int64_t nser, int64_t ser_stride, int64_t N, double fs, const double* b,
+              const int64_t* L, const int64_t* K, int64_t J, int32_t order, double psll, double* Sxx, double* enbw,
+              int32_t mem, void* stream);
+
 /* ---- Witness-based fitters (EXPERIMENTAL in the reference) ----
  * Replace, per record (main channel + witness channel):
  *   DFMI_WDFMI_NLS    WDFMI_NLSFitter.fit        fitters.py:481-570 (least_squares(method='lm'))
@@ -399,7 +437,9 @@ int dfmi_wdfmi_fit(const double* x, int64_t nrec, int64_t rec_stride, int64_t nb
  * the whole wave as 8 lambda rungs x 8 harmonic shares; 0: 8-lane groups each running the
  * whole fit; rounding only), "lm_ladder_split" (the ladder beyond 16 harmonics for at most this
  * many items per CU, default 4: one wave per item as 8 rungs x 8 harmonic shares; 0 = 8 lanes
- * per item; rounding only),
+ * per item; rounding only), "lpsd_batch_mb" (dfmi_lpsd: MiB of window and per-segment workspace
+ * per batch of frequencies, default 512; a batch holds at least one frequency, 0 = one frequency
+ * per batch; same bits),
  * "probe" (1 =
  * diagnostics timestamp buffer on the current device, dfmi_probe_read). */
 int dfmi_set_tuning(const char* key, int64_t value);
