@@ -31,7 +31,8 @@ SYMBOLS = ("dfmi_lm_config_default", "dfmi_demod", "dfmi_lm", "dfmi_nls_record",
            "dfmi_record_moments", "dfmi_synth_asd", "dfmi_synth_snr", "dfmi_bessel_eval",
            "dfmi_release_workspaces", "dfmi_step_timing", "dfmi_step_timing_read", "dfmi_ekf_pit_passes",
            "dfmi_ekf_pit_trace", "dfmi_demod_typed", "dfmi_demod_rows_typed", "dfmi_nls_record_typed",
-           "dfmi_fisher", "dfmi_lpsd_plan", "dfmi_lpsd")
+           "dfmi_fisher", "dfmi_lpsd_plan", "dfmi_lpsd", "dfmi_plnoise_design", "dfmi_plnoise",
+           "dfmi_synth_asd_coloured")
 
 
 class DFMIError(RuntimeError):
@@ -222,6 +223,12 @@ def load():
         lib.dfmi_record_moments.restype = ctypes.c_int
         lib.dfmi_synth_asd.argtypes = [P, i64, i64, dbl, P, i32, P]
         lib.dfmi_synth_asd.restype = ctypes.c_int
+        lib.dfmi_plnoise_design.argtypes = [dbl, i64, dbl, P, i32, P]
+        lib.dfmi_plnoise_design.restype = ctypes.c_int
+        lib.dfmi_plnoise.argtypes = [P, i32, dbl, dbl, P, i64, i64, i64, P, i32, P]
+        lib.dfmi_plnoise.restype = ctypes.c_int
+        lib.dfmi_synth_asd_coloured.argtypes = [P, P, P, i32, dbl, i64, i64, i64, dbl, P, i32, P]
+        lib.dfmi_synth_asd_coloured.restype = ctypes.c_int
         lib.dfmi_synth_snr.argtypes = [ctypes.POINTER(SnrParams), i64, i64, P, i32, P]
         lib.dfmi_synth_snr.restype = ctypes.c_int
         lib.dfmi_bessel_eval.argtypes = [P, i64, i32, i32, P, i32, P]

@@ -31,6 +31,7 @@
 #include "fork_guard.h"
 #include "moments.h"
 #include "synth.h"
+#include "plnoise.h"
 #include "wdfmi.h"
 #include "lpsd.h"
 
@@ -2152,9 +2153,87 @@ int dfmi_synth_asd(const dfmi_synth_trial* trials, int64_t ntrial, int64_t n_sam
   if ((rc = workspace(dev, "s_scratch", dfmi::synth_scratch_bytes(ntrial, n_samp), &scr))) return rc;
   if (mem != DFMI_MEM_DEVICE && (rc = workspace(dev, "s_out", ob, &dout))) return rc;
   HIPCHK(hipMemcpyAsync(dt, trials, (size_t)ntrial * sizeof(dfmi_synth_trial), hipMemcpyHostToDevice, st));
-  HIPCHK(dfmi::synth_launch((const dfmi_synth_trial*)dt, ntrial, n_samp, f_samp, scr, (double*)dout, st));
+  HIPCHK(dfmi::synth_launch((const dfmi_synth_trial*)dt, nullptr, nullptr, ntrial, n_samp, f_samp, scr, (double*)dout,
+                            st));
   if (mem != DFMI_MEM_DEVICE) HIPCHK(hipMemcpyAsync(out, dout, ob, hipMemcpyDeviceToHost, st));
   // the trial table is a caller (host) array: done with it only once the copy ran
+  HIPCHK(hipStreamSynchronize(st));
+  return DFMI_OK;
+}
+
+// the argument checks dfmi_plnoise and dfmi_synth_asd_coloured share (host side, before any device work)
+static int plnoise_args(const double* sections, int32_t nsec, double scale, int64_t n_warm, int64_t n) {
+  if (nsec > dfmi::kPlMaxSections) return fail(DFMI_ERR_UNSUPPORTED, "plnoise: more than 64 sections (one per lane)");
+  if (!sections || nsec < 1) return fail(DFMI_ERR_ARG, "plnoise: a section table of 1 <= nsec <= 64 rows is required");
+  if (n_warm < 0 || n < 1 || n_warm > INT64_MAX / 2 - n) return fail(DFMI_ERR_ARG, "plnoise: n_warm >= 0, n >= 1");
+  if (!std::isfinite(scale)) return fail(DFMI_ERR_ARG, "plnoise: scale must be finite");
+  for (int i = 0; i < 3 * nsec; ++i)
+    if (!std::isfinite(sections[i])) return fail(DFMI_ERR_ARG, "plnoise: a section coefficient is not finite");
+  return DFMI_OK;
+}
+
+int dfmi_plnoise(const double* sections, int32_t nsec, double scale, double sigma, const uint32_t* seeds,
+                 int64_t nser, int64_t n_warm, int64_t n, double* out, int32_t mem, void* stream) {
+  CallScope cs(stream);
+  int rc = plnoise_args(sections, nsec, scale, n_warm, n);
+  if (rc) return rc;
+  if (nser < 0 || nser > INT32_MAX || !std::isfinite(sigma)) return fail(DFMI_ERR_ARG, "plnoise: 0 <= nser < 2^31, sigma finite");
+  if (nser > 0 && (!seeds || !out)) return fail(DFMI_ERR_ARG, "null pointer");
+  int dev;
+  if ((rc = ensure_init(&dev))) return rc;
+  if (nser == 0) return DFMI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  void *dsec, *dseed, *dout = out;
+  const size_t ob = (size_t)nser * n * 8;
+  if ((rc = workspace(dev, "p_sections", (size_t)3 * nsec * 8, &dsec))) return rc;
+  if ((rc = workspace(dev, "p_seeds", (size_t)nser * 4, &dseed))) return rc;
+  if (mem != DFMI_MEM_DEVICE && (rc = workspace(dev, "p_out", ob, &dout))) return rc;
+  HIPCHK(hipMemcpyAsync(dsec, sections, (size_t)3 * nsec * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(dseed, seeds, (size_t)nser * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(dfmi::plnoise_launch((const double*)dsec, nsec, scale, (const uint32_t*)dseed, sigma, nullptr, nser, n_warm, n,
+                              (double*)dout, st));
+  if (mem != DFMI_MEM_DEVICE) HIPCHK(hipMemcpyAsync(out, dout, ob, hipMemcpyDeviceToHost, st));
+  // sections and seeds are caller (host) arrays: done with them only once the copies ran
+  HIPCHK(hipStreamSynchronize(st));
+  return DFMI_OK;
+}
+
+int dfmi_synth_asd_coloured(const dfmi_synth_trial* trials, const dfmi_synth_colour* colour, const double* sections,
+                            int32_t nsec, double scale, int64_t n_warm, int64_t ntrial, int64_t n_samp,
+                            double f_samp, double* out, int32_t mem, void* stream) {
+  bool any = false;
+  if (colour && ntrial > 0)
+    for (int64_t r = 0; r < ntrial; ++r) any = any || colour[r].g_freq != 0.0 || colour[r].g_arm != 0.0;
+  if (!any) return dfmi_synth_asd(trials, ntrial, n_samp, f_samp, out, mem, stream);
+  CallScope cs(stream);
+  if (ntrial > INT32_MAX || n_samp < 2 || !(f_samp > 0.0)) return fail(DFMI_ERR_ARG, "bad synthesis geometry (n_samp >= 2)");
+  if (!trials || !out) return fail(DFMI_ERR_ARG, "null pointer");
+  int rc = plnoise_args(sections, nsec, scale, n_warm, n_samp);
+  if (rc) return rc;
+  for (int64_t r = 0; r < ntrial; ++r)
+    if (!std::isfinite(colour[r].sigma) || !std::isfinite(colour[r].g_freq) || !std::isfinite(colour[r].g_arm) ||
+        !std::isfinite(colour[r].f0))
+      return fail(DFMI_ERR_ARG, "synth_asd_coloured: a colour row is not finite");
+  int dev;
+  if ((rc = ensure_init(&dev))) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  void *dt, *dc, *dsec, *scr, *basis, *dout = out;
+  const size_t ob = (size_t)ntrial * n_samp * 8;
+  if ((rc = workspace(dev, "s_trials", (size_t)ntrial * sizeof(dfmi_synth_trial), &dt))) return rc;
+  if ((rc = workspace(dev, "s_colour", (size_t)ntrial * sizeof(dfmi_synth_colour), &dc))) return rc;
+  if ((rc = workspace(dev, "p_sections", (size_t)3 * nsec * 8, &dsec))) return rc;
+  if ((rc = workspace(dev, "s_scratch", dfmi::synth_scratch_bytes(ntrial, n_samp), &scr))) return rc;
+  if ((rc = workspace(dev, "s_basis", ob, &basis))) return rc;
+  if (mem != DFMI_MEM_DEVICE && (rc = workspace(dev, "s_out", ob, &dout))) return rc;
+  HIPCHK(hipMemcpyAsync(dt, trials, (size_t)ntrial * sizeof(dfmi_synth_trial), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(dc, colour, (size_t)ntrial * sizeof(dfmi_synth_colour), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(dsec, sections, (size_t)3 * nsec * 8, hipMemcpyHostToDevice, st));
+  // the basis series of every coloured trial, then the trials over them (same stream: in order)
+  HIPCHK(dfmi::plnoise_launch((const double*)dsec, nsec, scale, nullptr, 0.0, (const dfmi_synth_colour*)dc, ntrial,
+                              n_warm, n_samp, (double*)basis, st));
+  HIPCHK(dfmi::synth_launch((const dfmi_synth_trial*)dt, (const dfmi_synth_colour*)dc, (const double*)basis, ntrial,
+                            n_samp, f_samp, scr, (double*)dout, st));
+  if (mem != DFMI_MEM_DEVICE) HIPCHK(hipMemcpyAsync(out, dout, ob, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   return DFMI_OK;
 }

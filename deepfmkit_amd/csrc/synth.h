@@ -208,19 +208,44 @@ DFMI_SY_HD double synth_v(const dfmi_synth_trial& p, int64_t k, double f_samp, d
   return (p.df + nz_df) * gn;
 }
 
-// The signal at sample k from phi_mod (the whole vector) and the amplitude noise
+// The signal at sample k from phi_mod (the whole vector), the amplitude noise, the
+// arm-length noise (dynamic channels only) and the carrier's angular frequency w0
+// (physics.py:685-702): w0c without frequency noise, synth_w0 with it
 template <typename Arr>
-DFMI_SY_HD double synth_signal(const dfmi_synth_trial& p, int64_t k, int64_t n, double f_samp, const Arr& phi,
-                               double nz_amp) {
+DFMI_SY_HD double synth_signal_at(const dfmi_synth_trial& p, int64_t k, int64_t n, double f_samp, const Arr& phi,
+                                  double nz_amp, double nz_arm, double w0) {
 #pragma clang fp contract(off)
   const double t = (double)k / f_samp;
-  const double dl = p.dynamic ? (p.arml_mod_amp * sin(p.w_arm * t + p.arml_mod_psi) + 0.0) + p.dl0 : p.dl0;
+  const double dl = p.dynamic ? (p.arml_mod_amp * sin(p.w_arm * t + p.arml_mod_psi) + nz_arm) + p.dl0 : p.dl0;
   const double tau_dl = dl / p.c_light;
   const double pm_meas = interp_grid(t - (p.tau_m + tau_dl), phi, n, f_samp);
   const double pm_ref = interp_grid(t - p.tau_r, phi, n, f_samp);
-  const double phase = p.w0c * ((p.tau_m + tau_dl) - p.tau_r) + (pm_meas - pm_ref);
+  const double phase = w0 * ((p.tau_m + tau_dl) - p.tau_r) + (pm_meas - pm_ref);
   const double amp = p.amp + nz_amp;
   return amp * (1.0 + p.vis * cos(phase));
+}
+
+// 2 * np.pi * (c / wavelength + laser_frequency[k])
+DFMI_SY_HD double synth_w0(double f0, double nz_freq) {
+#pragma clang fp contract(off)
+  return 6.283185307179586 * (f0 + nz_freq);
+}
+
+// The signal without coloured sources (dfmi_synth_asd)
+template <typename Arr>
+DFMI_SY_HD double synth_signal(const dfmi_synth_trial& p, int64_t k, int64_t n, double f_samp, const Arr& phi,
+                               double nz_amp) {
+  return synth_signal_at(p, k, n, f_samp, phi, nz_amp, 0.0, p.w0c);
+}
+
+// The signal with the coloured sources of `c` over its basis series (dfmi_synth_asd_coloured)
+template <typename Arr, typename Basis>
+DFMI_SY_HD double synth_signal_coloured(const dfmi_synth_trial& p, const dfmi_synth_colour& c, int64_t k, int64_t n,
+                                        double f_samp, const Arr& phi, double nz_amp, const Basis& basis) {
+#pragma clang fp contract(off)
+  const double nz_arm = c.g_arm != 0.0 ? c.g_arm * basis(k) : 0.0;
+  const double w0 = c.g_freq != 0.0 ? synth_w0(c.f0, c.g_freq * basis(k)) : p.w0c;
+  return synth_signal_at(p, k, n, f_samp, phi, nz_amp, nz_arm, w0);
 }
 
 // One trial, one lane (the host check's form; the device runs the same helpers with
@@ -248,11 +273,32 @@ DFMI_SY_HD void synth_trial(const dfmi_synth_trial& p, int64_t n, double f_samp,
   for (int64_t k = 0; k < n; ++k) out(k) = synth_signal(p, k, n, f_samp, phi, nz_amp(k));
 }
 
+// synth_trial with the coloured sources of `c` over basis(0..n) (plnoise.h pl_series)
+template <typename Key, typename Vec, typename Out>
+DFMI_SY_HD void synth_trial_coloured(const dfmi_synth_trial& p, const dfmi_synth_colour& c, int64_t n, double f_samp,
+                                     Key key, Vec nz_amp, Vec nz_df, Vec phi, Vec basis, Out out) {
+#pragma clang fp contract(off)
+  Mt<Key> mt{key, 0, false, 0.0};
+  mt.seed(p.seed);
+  for (int64_t k = 0; k < n; ++k) nz_amp(k) = p.s_amp != 0.0 ? 0.0 + p.s_amp * mt.next_gauss() : 0.0;
+  for (int64_t k = 0; k < n; ++k) nz_df(k) = p.s_df != 0.0 ? 0.0 + p.s_df * mt.next_gauss() : 0.0;
+  double gmax = 0.0;
+  for (int64_t k = 0; k < n; ++k) gmax = synth_gmax_step(gmax, fabs(synth_g(p, k, f_samp)));
+  double acc = 0.0;
+  for (int64_t k = 0; k < n; ++k) {
+    const double v = synth_v(p, k, f_samp, gmax, nz_df(k));
+    acc = k == 0 ? v : acc + v;
+    phi(k) = p.cphi * acc;
+  }
+  for (int64_t k = 0; k < n; ++k) out(k) = synth_signal_coloured(p, c, k, n, f_samp, phi, nz_amp(k), basis);
+}
+
 #if defined(__HIPCC__)
-// synth.hip: scratch bytes for ntrial trials of n samples, and the launch.
+// synth.hip: scratch bytes for ntrial trials of n samples, and the launch. colour / basis
+// (device: ntrial rows / ntrial x n, from plnoise.hip) or both NULL (dfmi_synth_asd).
 size_t synth_scratch_bytes(int64_t ntrial, int64_t n);
-hipError_t synth_launch(const dfmi_synth_trial* d_trials, int64_t ntrial, int64_t n, double f_samp, void* scratch,
-                        double* out, hipStream_t st);
+hipError_t synth_launch(const dfmi_synth_trial* d_trials, const dfmi_synth_colour* d_colour, const double* d_basis,
+                        int64_t ntrial, int64_t n, double f_samp, void* scratch, double* out, hipStream_t st);
 #endif
 
 }  // namespace dfmi

@@ -14,21 +14,25 @@
 // Built without FMA contraction (synth.h also pins it per function).
 #include <hip/hip_runtime.h>
 
+#include "mt_wave.h"
 #include "synth.h"
 
 namespace dfmi {
 namespace {
 
-constexpr int kLanes = 64;
-constexpr int kWordsPerLane = (kMtN + kLanes - 1) / kLanes;  // 10
-constexpr int kCandidates = kMtN / 4;                        // 156 per twisted block
+constexpr int kLanes = kMtLanes;
 
 struct GVec {
   const double* p;
   __device__ __forceinline__ double operator()(int64_t k) const { return p[k]; }
 };
 
-__global__ __launch_bounds__(kLanes) void synth_wave_kernel(const dfmi_synth_trial* __restrict__ trials, int64_t n,
+// kColour: the trial's coloured sources scale its basis series (plnoise.hip wrote it);
+// false is dfmi_synth_asd's kernel, which names neither table.
+template <bool kColour>
+__global__ __launch_bounds__(kLanes) void synth_wave_kernel(const dfmi_synth_trial* __restrict__ trials,
+                                                             const dfmi_synth_colour* __restrict__ colour,
+                                                             const double* __restrict__ basis_all, int64_t n,
                                                              double f_samp, double* scratch, double* out) {
 #pragma clang fp contract(off)
   __shared__ uint32_t mt[kMtN];
@@ -40,64 +44,21 @@ __global__ __launch_bounds__(kLanes) void synth_wave_kernel(const dfmi_synth_tri
   const bool amp_on = p.s_amp != 0.0, df_on = p.s_df != 0.0;
   const int64_t need = (amp_on ? n : 0) + (df_on ? n : 0);
 
-  // numpy mt19937_seed
-  if (lane == 0) {
-    uint32_t s = p.seed;
-    for (int i = 0; i < kMtN; ++i) {
-      mt[i] = s;
-      s = 1812433253u * (s ^ (s >> 30)) + (uint32_t)(i + 1);
-    }
-  }
-  __syncthreads();
+  mt_wave_seed(mt, p.seed, lane);
 
   int64_t have = 0;
   while (have < need) {
-    // twist: old operands into registers first, then the three phases
-    uint32_t o0[kWordsPerLane], o1[kWordsPerLane];
-#pragma unroll
-    for (int j = 0; j < kWordsPerLane; ++j) {
-      const int i = lane + kLanes * j;
-      o0[j] = i < kMtN ? mt[i] : 0u;
-      o1[j] = i < kMtN - 1 ? mt[i + 1] : 0u;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < kWordsPerLane; ++j) {
-      const int i = lane + kLanes * j;
-      if (i < kMtN - kMtM) mt[i] = mt_twist_word(o0[j], o1[j], mt[i + kMtM]);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < kWordsPerLane; ++j) {
-      const int i = lane + kLanes * j;
-      if (i >= kMtN - kMtM && i < 2 * (kMtN - kMtM)) mt[i] = mt_twist_word(o0[j], o1[j], mt[i + (kMtM - kMtN)]);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < kWordsPerLane; ++j) {
-      const int i = lane + kLanes * j;
-      if (i >= 2 * (kMtN - kMtM) && i < kMtN - 1) mt[i] = mt_twist_word(o0[j], o1[j], mt[i + (kMtM - kMtN)]);
-    }
-    __syncthreads();
-    if (lane == (kMtN - 1) % kLanes) mt[kMtN - 1] = mt_twist_word(o0[(kMtN - 1) / kLanes], mt[0], mt[kMtM - 1]);
-    __syncthreads();
+    mt_wave_twist(mt, lane);
     // the block's 156 candidates in stream order
-    for (int c0 = 0; c0 < kCandidates && have < need; c0 += kLanes) {
-      const int c = c0 + lane;
-      double x1 = 0.0, x2 = 0.0, r2 = 0.0;
-      bool ok = false;
-      if (c < kCandidates)
-        ok = polar_candidate(mt_temper(mt[4 * c]), mt_temper(mt[4 * c + 1]), mt_temper(mt[4 * c + 2]),
-                             mt_temper(mt[4 * c + 3]), &x1, &x2, &r2);
-      const uint64_t bal = __ballot(ok);
-      const int rank = __popcll(bal & ((1ull << lane) - 1ull));
-      const int64_t idx = have + 2 * (int64_t)rank;
-      if (ok && idx < need) {
-        const double f = polar_scale(r2);
-        gauss[idx] = f * x2;
-        gauss[idx + 1] = f * x1;
-      }
-      have += 2 * (int64_t)__popcll(bal);
+    for (int c0 = 0; c0 < kMtCandidates && have < need; c0 += kLanes) {
+      const int64_t base = have;
+      have += mt_wave_polar(mt, c0, lane, [=](int rel, double g0, double g1) {
+        const int64_t idx = base + rel;
+        if (idx < need) {
+          gauss[idx] = g0;
+          gauss[idx + 1] = g1;
+        }
+      });
     }
     __syncthreads();
   }
@@ -135,6 +96,15 @@ __global__ __launch_bounds__(kLanes) void synth_wave_kernel(const dfmi_synth_tri
   __syncthreads();
   const GVec ph{phi};
   double* o = out + r * n;
+  if constexpr (kColour) {
+    const dfmi_synth_colour c = colour[r];
+    const GVec basis{basis_all + r * n};
+    if (c.g_freq != 0.0 || c.g_arm != 0.0) {
+      for (int64_t k = lane; k < n; k += kLanes)
+        o[k] = synth_signal_coloured(p, c, k, n, f_samp, ph, n_amp ? 0.0 + p.s_amp * n_amp[k] : 0.0, basis);
+      return;
+    }
+  }
   for (int64_t k = lane; k < n; k += kLanes)
     o[k] = synth_signal(p, k, n, f_samp, ph, n_amp ? 0.0 + p.s_amp * n_amp[k] : 0.0);
 }
@@ -143,11 +113,15 @@ __global__ __launch_bounds__(kLanes) void synth_wave_kernel(const dfmi_synth_tri
 
 size_t synth_scratch_bytes(int64_t ntrial, int64_t n) { return (size_t)ntrial * (3 * n + 2) * 8; }
 
-hipError_t synth_launch(const dfmi_synth_trial* d_trials, int64_t ntrial, int64_t n, double f_samp, void* scratch,
-                        double* out, hipStream_t st) {
+hipError_t synth_launch(const dfmi_synth_trial* d_trials, const dfmi_synth_colour* d_colour, const double* d_basis,
+                        int64_t ntrial, int64_t n, double f_samp, void* scratch, double* out, hipStream_t st) {
   if (ntrial == 0) return hipSuccess;
-  hipLaunchKernelGGL(synth_wave_kernel, dim3((unsigned)ntrial), dim3(kLanes), 0, st, d_trials, n, f_samp,
-                     (double*)scratch, out);
+  if (d_colour && d_basis)
+    hipLaunchKernelGGL(synth_wave_kernel<true>, dim3((unsigned)ntrial), dim3(kLanes), 0, st, d_trials, d_colour,
+                       d_basis, n, f_samp, (double*)scratch, out);
+  else
+    hipLaunchKernelGGL(synth_wave_kernel<false>, dim3((unsigned)ntrial), dim3(kLanes), 0, st, d_trials, nullptr,
+                       nullptr, n, f_samp, (double*)scratch, out);
   return hipGetLastError();
 }
 

@@ -2,9 +2,16 @@
 
 Only what the NLS readout path needs as INPUT is restated here (SURVEY.md §8a row
 a16): the configuration containers and the snr-mode generator of
-physics.py:475-530, plus the zero/white-noise subset of the asd mode used by
-workers.run_single_trial (physics.py:423-473, 615-722).  Coloured (1/f^alpha)
-noise needs `pyplnoise`, which is absent from this image: requesting it raises.
+physics.py:475-530, plus the asd mode used by workers.run_single_trial
+(physics.py:423-473, 615-722) with its white (amplitude, df) and coloured
+(laser frequency, arm length: 1/f^2) noise sources.
+
+The coloured sources are the project's OWN generator: a pole-zero
+cascade (Plaszczynski 2007) over numpy's legacy RandomState stream, designed by
+alpha_noise_design and run by scipy.signal.lfilter on the host or by dfmi_plnoise on
+the GPU. The reference draws them with `pyplnoise`, which is not available here:
+parity with pyplnoise's streams is NOT pinned (the spectra agree by construction,
+the sample values do not).
 
 The snr-mode restatement keeps the reference's numpy operation order, so for a
 given seed the generated record is bit-identical to the reference's (pinned by
@@ -159,12 +166,75 @@ def add_white_noise(clean, snr_db, trial_num):
     return clean + rng.randn(len(clean)) * std
 
 
+ALPHA_MAX_SECTIONS = 64  # dfmi_plnoise runs one section per lane of a wave
+
+
+def alpha_noise_design(fs, n, alpha):
+    """(sections, scale) of the 1/f^alpha cascade for a record of n samples at rate fs:
+    sections is (nsec, 3) float64, rows (a0, a1, b1), from dfmi_plnoise_design (host only,
+    no GPU needed), so host and device filter with one table. ValueError for n < 4, alpha
+    outside (0, 2] or more than 64 sections."""
+    from . import _lib
+    lib = _lib.load()
+    sec = np.zeros((ALPHA_MAX_SECTIONS, 3), dtype=np.float64)
+    scale = np.zeros(1, dtype=np.float64)
+    nsec = lib.dfmi_plnoise_design(float(fs), int(n), float(alpha), sec.ctypes.data, ALPHA_MAX_SECTIONS,
+                                   scale.ctypes.data)
+    if nsec < 0:
+        raise ValueError(f"alpha_noise_design(fs={fs}, n={n}, alpha={alpha}): "
+                         + ("more than 64 sections" if nsec == -4 else "needs n >= 4, fs > 0, 0 < alpha <= 2"))
+    return np.ascontiguousarray(sec[:nsec]), float(scale[0])
+
+
+def _alpha_noise_host(sections, scale, sigma, seed, n_warm, n):
+    """One basis series on the host: RandomState(seed).normal(scale=sigma), each section
+    by scipy.signal.lfilter in turn (zero initial state), scale * y[n_warm:]."""
+    from scipy.signal import lfilter
+    x = np.random.RandomState(seed=seed).normal(scale=sigma, size=int(n_warm) + int(n))
+    for a0, a1, b1 in sections:
+        x = lfilter([a0, a1], [1.0, -b1], x)
+    return scale * x[int(n_warm):]
+
+
+def alpha_noise(fs, n, alpha, seeds, device=None):
+    """1/f^alpha series of unit-ASD scale (PSD ~ f^-alpha between ~4 fs/n and fs/8), one per
+    seed: (len(seeds), n). device None: numpy, on the host (scipy.signal.lfilter);
+    'cuda' (or a torch device): a CUDA tensor from dfmi_plnoise, which agrees with the host
+    series to the device's log. Warm-up: 2 n samples."""
+    sections, scale = alpha_noise_design(fs, n, alpha)
+    seeds = np.ascontiguousarray(np.atleast_1d(np.asarray(seeds, dtype=np.int64)))
+    if seeds.size and (seeds.min() < 0 or seeds.max() > 2 ** 32 - 1):
+        raise ValueError("Seed must be between 0 and 2**32 - 1")
+    n, sigma = int(n), float(np.sqrt(fs / 2.0))
+    if device is None:
+        return np.stack([_alpha_noise_host(sections, scale, sigma, int(s), 2 * n, n) for s in seeds]) \
+            if seeds.size else np.zeros((0, n))
+    import torch
+
+    from . import _lib
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise ValueError("alpha_noise: device must be None (host) or a CUDA device")
+    s32 = seeds.astype(np.uint32)
+    with torch.cuda.device(dev):
+        out = torch.empty((seeds.size, n), dtype=torch.float64, device=dev)
+        _lib.check(_lib.load().dfmi_plnoise(sections.ctypes.data, len(sections), scale, sigma, s32.ctypes.data,
+                                            seeds.size, 2 * n, n, out.data_ptr(), _lib.DFMI_MEM_DEVICE,
+                                            torch.cuda.current_stream(dev).cuda_stream), "dfmi_plnoise")
+    return out
+
+
 def asd_noise_arrays(cfg, n_samples, trial_num=0):
-    """physics.py:532-613, white/zero sources only (coloured needs pyplnoise)."""
+    """physics.py:532-613 in the reference's order: the white sources from
+    RandomState(1 + 4 trial_num); the coloured ones (both alpha = 2) scale ONE basis series
+    drawn from RandomState(2 + 4 trial_num) (the reference's basis_noises dictionary shares
+    it; the series itself is this project's generator, not pyplnoise's). A source whose ASD
+    is 0 stays the scalar 0.0."""
     fs = cfg.f_samp
     params = [("laser_frequency", cfg.laser.f_n, 2.0), ("amplitude", cfg.laser.amp_n, 0.0),
               ("df", cfg.laser.df_n, 0.0), ("armlength", cfg.ifo.arml_mod_n, 2.0)]
     rng = np.random.RandomState(seed=1 + trial_num * len(params))
+    basis = None
     out = {}
     for name, asd, alpha in params:
         if asd == 0.0:
@@ -172,8 +242,11 @@ def asd_noise_arrays(cfg, n_samples, trial_num=0):
         elif name in ("amplitude", "df"):
             out[name] = rng.normal(scale=asd * np.sqrt(fs / 2.0), size=int(n_samples))
         else:
-            raise NotImplementedError(
-                f"coloured '{name}' noise (alpha={alpha}) needs pyplnoise, which is not installed")
+            if basis is None:
+                n = int(n_samples)
+                sections, scale = alpha_noise_design(fs, n, alpha)
+                basis = _alpha_noise_host(sections, scale, np.sqrt(fs / 2.0), 2 + trial_num * len(params), 2 * n, n)
+            out[name] = asd / np.sqrt(2) * basis
     return out
 
 
@@ -262,10 +335,14 @@ def _put_waveform(rec, wf):
 def device_synth_supported(cfg) -> bool:
     """dfmi_synth_asd covers the default cosine waveform and the waveforms of
     waveforms.py (second-harmonic distortion, triangle, square, dfm-like, dfm) with
-    scalar arguments, white (or zero) amplitude / df noise and no frequency /
-    arm-length noise sources."""
-    laser, ifo = cfg.laser, cfg.ifo
-    return _device_waveform(laser) is not None and laser.f_n == 0.0 and ifo.arml_mod_n == 0.0
+    scalar arguments, white (or zero) amplitude / df noise; dfmi_synth_asd_coloured adds
+    the coloured frequency / arm-length sources (any record whose cascade has at most 64
+    sections: every record length >= 4 the project can hold)."""
+    return _device_waveform(cfg.laser) is not None
+
+
+def _coloured(cfg) -> bool:
+    return cfg.laser.f_n != 0.0 or cfg.ifo.arml_mod_n != 0.0
 
 
 def synth_trial_fields(cfg, trial_num, dynamic=True):
@@ -312,7 +389,7 @@ def synth_trial_table(cfgs, trial_nums, dynamic=True):
     n = len(cfgs)
     if any(not device_synth_supported(c) for c in cfgs):
         bad = [i for i, c in enumerate(cfgs) if not device_synth_supported(c)]
-        raise ValueError(f"trials {bad[:5]} need the host generator (custom waveform or coloured noise)")
+        raise ValueError(f"trials {bad[:5]} need the host generator (custom waveform)")
     f_samp = float(cfgs[0].f_samp)
     if any(float(c.f_samp) != f_samp for c in cfgs):
         raise ValueError("synthesize_asd_trials: trials must share f_samp")
@@ -355,11 +432,34 @@ def synth_trial_table(cfgs, trial_nums, dynamic=True):
     return tab
 
 
+SYNTH_COLOUR_DTYPE = np.dtype([("seed", "<u4"), ("pad", "<i4"), ("sigma", "<f8"), ("g_freq", "<f8"),
+                               ("g_arm", "<f8"), ("f0", "<f8")])  # dfmi_synth_colour
+
+
+def synth_colour_table(cfgs, trial_nums):
+    """dfmi_synth_colour rows for many (cfg, trial_num): the scalar sub-expressions of the
+    coloured sources in asd_noise_arrays and exact_model_signal, evaluated as numpy does."""
+    n = len(cfgs)
+    seeds = 2 + np.asarray(trial_nums, dtype=np.int64) * 4
+    if seeds.size and (seeds.min() < 0 or seeds.max() > 2 ** 32 - 1):
+        raise ValueError("Seed must be between 0 and 2**32 - 1")
+    f_samp = float(cfgs[0].f_samp) if n else 1.0
+    tab = np.zeros(n, dtype=SYNTH_COLOUR_DTYPE)
+    tab["seed"] = seeds.astype(np.uint32)
+    tab["sigma"] = np.sqrt(f_samp / 2.0)
+    tab["g_freq"] = np.fromiter((c.laser.f_n for c in cfgs), dtype=np.float64, count=n) / np.sqrt(2)
+    tab["g_arm"] = np.fromiter((c.ifo.arml_mod_n for c in cfgs), dtype=np.float64, count=n) / np.sqrt(2)
+    tab["f0"] = sc.c / np.fromiter((c.laser.wavelength for c in cfgs), dtype=np.float64, count=n)
+    return tab
+
+
 def synthesize_asd_trials(cfgs, trial_nums, n_seconds, dynamic=True):
     """The main channel (dynamic=True) or a witness channel (dynamic=False) of
     SignalGenerator.generate(cfg, n_seconds, mode='asd', trial_num=t) for every (cfg, t),
-    generated on the GPU (dfmi_synth_asd) into one (ntrial, N) CUDA tensor. All cfgs
-    share f_samp; each must be device_synth_supported."""
+    generated on the GPU into one (ntrial, N) CUDA tensor: dfmi_synth_asd, or
+    dfmi_synth_asd_coloured when any trial has frequency / arm-length noise (one section
+    table: the trials share N and f_samp). All cfgs share f_samp; each must be
+    device_synth_supported."""
     import torch
 
     from . import _lib
@@ -369,6 +469,13 @@ def synthesize_asd_trials(cfgs, trial_nums, n_seconds, dynamic=True):
     n = int(n_seconds * f_samp)
     out = torch.empty((len(cfgs), n), dtype=torch.float64, device="cuda")
     lib = _lib.load()
+    if any(_coloured(c) for c in cfgs):
+        col = synth_colour_table(cfgs, trial_nums)
+        sections, scale = alpha_noise_design(f_samp, n, 2.0)
+        _lib.check(lib.dfmi_synth_asd_coloured(tab.ctypes.data, col.ctypes.data, sections.ctypes.data, len(sections),
+                                               scale, 2 * n, len(cfgs), n, f_samp, out.data_ptr(),
+                                               _lib.DFMI_MEM_DEVICE, _torch_stream()), "dfmi_synth_asd_coloured")
+        return out
     _lib.check(lib.dfmi_synth_asd(tab.ctypes.data, len(cfgs), n, f_samp, out.data_ptr(), _lib.DFMI_MEM_DEVICE,
                                   _torch_stream()), "dfmi_synth_asd")
     return out

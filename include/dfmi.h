@@ -42,6 +42,10 @@
  *                    and the per-segment standard errors of a fit (no reference counterpart)
  *   dfmi_lpsd_plan,  DeepFitObject.calc_lpsd / DeepFitFramework.calc_lpsd (data.py:239-244,
  *   dfmi_lpsd        core.py:590-609), with this project's own definition of the estimator
+ *   dfmi_plnoise_design, dfmi_plnoise, dfmi_synth_asd_coloured
+ *                    the coloured (1/f^2) frequency and arm-length noise of the asd mode
+ *                    (physics.py:570-611, 685-702), with this project's own generator in
+ *                    place of pyplnoise's
  */
 #ifndef DFMI_H
 #define DFMI_H
@@ -260,6 +264,53 @@ typedef struct dfmi_synth_trial {
  * (the device's cos / sin / log), bit-exact elsewhere. */
 int dfmi_synth_asd(const dfmi_synth_trial* trials, int64_t ntrial, int64_t n_samp, double f_samp, double* out,
                    int32_t mem, void* stream);
+
+/* ---- Coloured (1/f^alpha) noise: the pole-zero cascade of Plaszczynski (2007) ----
+ * The project's own definition; the reference draws these sources
+ * with pyplnoise (physics.py:570-611), whose streams are NOT reproduced.
+ *
+ * dfmi_plnoise_design: host only, all arithmetic double. For a record of n >= 4 samples at
+ * rate fs > 0 and 0 < alpha <= 2: f_min = fs/n, f_max = fs/2, lw = log10(2 pi f),
+ * nsec = ceil(4.5 (lw1 - lw0)), dp = (lw1 - lw0)/nsec and, for section i,
+ *   lp = lw0 + dp 0.5 ((2i + 1) - alpha/2),  f0 = 10^lp / 2 pi,  f1 = 10^(lp + dp alpha/2) / 2 pi,
+ *   a0 = (fs + pi f1)/(fs + pi f0),  a1 = -(fs - pi f1)/(fs + pi f0),  b1 = (fs - pi f0)/(fs + pi f0),
+ * sections[3i + (0, 1, 2)] = a0, a1, b1 and *scale = f_max^(-alpha/2). Returns nsec,
+ * DFMI_ERR_ARG for arguments outside those ranges (or cap < nsec), DFMI_ERR_UNSUPPORTED
+ * where nsec > 64. sections == NULL only counts; scale may be NULL. It sets no
+ * dfmi_last_error message. */
+int dfmi_plnoise_design(double fs, int64_t n, double alpha, double* sections, int32_t cap, double* scale);
+
+/* dfmi_plnoise: out[r*n + k] = scale * y_r[n_warm + k], where y_r is
+ * x = RandomState(seeds[r]).normal(scale = sigma, size = n_warm + n) run through the sections
+ * in order with zero initial state (y[k] = a0 x[k] + z, z = a1 x[k] + b1 y[k]; each
+ * operation rounded, scipy.signal.lfilter's arithmetic). One wave per series, a section per
+ * lane. sections (any table, 1 <= nsec <= 64; DFMI_ERR_UNSUPPORTED above) and seeds: host
+ * arrays; out in `mem`. The warm-up samples never reach memory. The gaussians are numpy's up
+ * to the device's log (within an ulp of libm's); the filter arithmetic is IEEE. */
+int dfmi_plnoise(const double* sections, int32_t nsec, double scale, double sigma, const uint32_t* seeds,
+                 int64_t nser, int64_t n_warm, int64_t n, double* out, int32_t mem, void* stream);
+
+/* The coloured sources of one asd-mode trial: both alpha = 2 sources scale ONE basis series
+ * (as the reference's basis_noises dictionary shares it), drawn by dfmi_plnoise's generator. */
+typedef struct dfmi_synth_colour {
+  uint32_t seed;   /* 2 + trial_num * 4 */
+  int32_t pad;
+  double sigma;    /* np.sqrt(f_samp / 2.0) */
+  double g_freq;   /* laser.f_n / np.sqrt(2): laser_frequency = g_freq * basis; 0: source absent */
+  double g_arm;    /* ifo.arml_mod_n / np.sqrt(2): armlength = g_arm * basis; 0: source absent */
+  double f0;       /* c / laser.wavelength: the carrier is 2 pi (f0 + laser_frequency[k]), which
+                      dfmi_synth_trial.w0c = 2 pi f0 does not give back exactly */
+} dfmi_synth_colour;
+
+/* dfmi_synth_asd with coloured frequency / arm-length noise (physics.py:685-702):
+ *   dl = (A sin(..) + armlength[k]) + dl0 on dynamic channels (a witness sees none),
+ *   phase = (2 pi (f0 + laser_frequency[k])) * ((tau_m + tau_dl) - tau_r) + ...
+ * trials, colour (ntrial rows, or NULL) and sections are host arrays; every trial shares the
+ * section table (one n_samp and f_samp per call). colour == NULL, and every row whose gains
+ * are both 0, gives exactly dfmi_synth_asd's bits. */
+int dfmi_synth_asd_coloured(const dfmi_synth_trial* trials, const dfmi_synth_colour* colour, const double* sections,
+                            int32_t nsec, double scale, int64_t n_warm, int64_t ntrial, int64_t n_samp,
+                            double f_samp, double* out, int32_t mem, void* stream);
 
 /* ---- Counter-based snr-mode input (bench / tests of sharded records) ----
  * The signal of SignalGenerator._generate_with_snr (physics.py:475-530, ideal signal
