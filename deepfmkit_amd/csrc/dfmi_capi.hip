@@ -216,14 +216,15 @@ thread_local DeviceState* t_ds = nullptr;  // the device of the current call
 int ensure_init_locked(int* dev_out);
 
 // Picks (and on first use initialises) the current HIP device and takes its lock
-// for the rest of the current CallScope.
-int ensure_init(int* dev_out) {
+// for the rest of the current CallScope; t_ds is that device from here on.
+int ensure_init() {
   DeviceState* ds = nullptr;
   {
     std::lock_guard<std::mutex> g(g_mu);
-    int rc = ensure_init_locked(dev_out);
+    int dev = 0;
+    int rc = ensure_init_locked(&dev);
     if (rc) return rc;
-    ds = &g_dev[*dev_out];
+    ds = &g_dev[dev];
   }
   if (t_call && !t_call->dev_lk.owns_lock()) t_call->dev_lk = std::unique_lock<std::mutex>(ds->mu);
   t_ds = ds;
@@ -323,8 +324,7 @@ int free_stream_ws(StreamWs& s) {
 // first waits for the device to drain and frees the least recently used stream's set
 // (include/dfmi.h: a caller cycling over more streams than that serialises on the device,
 // and such a call cannot be captured into a graph).
-int workspace(int dev, const char* name, size_t bytes, void** out) {
-  (void)dev;
+int workspace(const char* name, size_t bytes, void** out) {
   const uintptr_t key = t_call ? (uintptr_t)t_call->stream : 0;
   DeviceState& ds = *t_ds;
   auto it = ds.ws.find(key);
@@ -352,19 +352,92 @@ int workspace(int dev, const char* name, size_t bytes, void** out) {
   return DFMI_OK;
 }
 
+// Staging of one entry point's `mem` argument on the caller's stream. in(): the caller's pointer
+// in device mode; in host mode workspace `name`, filled by hipMemcpyAsync. out(): the caller's
+// pointer in device mode; in host mode workspace `name`, copied back by finish(). upload(): an
+// array that is the caller's HOST memory in both modes (a parameter table): always a filled
+// workspace, and finish() then synchronises in device mode too, since the caller may free the
+// array once the call returns. finish(): the device-to-host copies in the order their outputs
+// were registered, then the call's one hipStreamSynchronize (host mode, or after an upload()).
+// A workspace holds at least 8 bytes and an empty copy is not issued, so an empty array still
+// has a device address. A new entry point uses this; the ones that stage by hand (dfmi_fisher's
+// packed rows, dfmi_lpsd's strided series, dfmi_lm's device-to-device results, the row layout's
+// support check between allocation and upload, the EKF's init4 rows) say why.
+struct Staging {
+  const bool host;
+  const hipStream_t st;
+  bool sync;
+  struct Back { void* dst; const void* src; size_t bytes; };
+  std::vector<Back> back;  // host mode only
+  Staging(int32_t mem, hipStream_t s) : host(mem != DFMI_MEM_DEVICE), st(s), sync(host) {}
+  int fill(const char* name, const void* p, size_t bytes, void** dev) {
+    if (int rc = workspace(name, bytes ? bytes : 8, dev)) return rc;
+    if (bytes) HIPCHK(hipMemcpyAsync(*dev, p, bytes, hipMemcpyHostToDevice, st));
+    return DFMI_OK;
+  }
+  template <typename T>
+  int in(const char* name, const T* p, size_t bytes, const T** dev) {
+    *dev = p;
+    return host ? fill(name, p, bytes, (void**)dev) : DFMI_OK;
+  }
+  template <typename T>
+  int upload(const char* name, const T* p, size_t bytes, const T** dev) {
+    sync = true;
+    return fill(name, p, bytes, (void**)dev);
+  }
+  template <typename T>
+  int out(const char* name, T* p, size_t bytes, T** dev) {
+    *dev = p;
+    if (!host) return DFMI_OK;
+    if (int rc = workspace(name, bytes ? bytes : 8, (void**)dev)) return rc;
+    if (bytes) back.push_back({p, *dev, bytes});
+    return DFMI_OK;
+  }
+  int finish() {
+    for (const Back& b : back) HIPCHK(hipMemcpyAsync(b.dst, b.src, b.bytes, hipMemcpyDeviceToHost, st));
+    if (sync) HIPCHK(hipStreamSynchronize(st));
+    return DFMI_OK;
+  }
+};
+
+// The cached device tables (pairwise plans, basis tables, m-grid Bessel tables) all come from
+// here: map[key] when present; otherwise fill(&aux) builds the bytes on the host (a std::vector)
+// and they are uploaded (hipMalloc + hipMemcpy). The entry joins the map only after the upload
+// succeeded: a failed hipMalloc or hipMemcpy leaves no buffer and no entry behind, so the next
+// call with that key builds the table again and never runs kernels on one that was not filled.
+// aux: a value the fill may keep beside the table (pwplan: the leaves of the plan).
+template <typename Map, typename Fill>
+int cached_upload(Map& map, const typename Map::key_type& key, Fill fill, const DevBuf** out) {
+  auto it = map.find(key);
+  if (it == map.end()) {
+    DevBuf b;
+    const auto h = fill(&b.aux);
+    b.n = h.size() * sizeof(h[0]);
+    HIPCHK(hipMalloc(&b.p, b.n));
+    const hipError_t e = hipMemcpy(b.p, h.data(), b.n, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      (void)hipFree(b.p);
+      return fail(DFMI_ERR_HIP, std::string("hipMemcpy(b.p, h.data(), b.n, hipMemcpyHostToDevice) failed: ") +
+                                    hipGetErrorString(e));
+    }
+    it = map.emplace(key, b).first;
+  }
+  *out = &it->second;
+  return DFMI_OK;
+}
+
 // Device copy of numpy's summation plan over n elements (np_sum.h), cached per n;
 // n_leaves (optional) = plan[0].
-int pairwise_plan(int dev, int64_t n, const int** out, int64_t* n_leaves) {
-  DevBuf& pb = t_ds->pwplan[n];
-  if (!pb.p) {
-    const std::vector<int> plan = dfmi_pairwise_plan((int)n);
-    HIPCHK(hipMalloc(&pb.p, plan.size() * sizeof(int)));
-    pb.n = plan.size() * sizeof(int);
-    HIPCHK(hipMemcpy(pb.p, plan.data(), pb.n, hipMemcpyHostToDevice));
-    pb.aux = plan[0];
-  }
-  *out = (const int*)pb.p;
-  if (n_leaves) *n_leaves = pb.aux;
+int pairwise_plan(int64_t n, const int** out, int64_t* n_leaves) {
+  const DevBuf* pb;
+  if (int rc = cached_upload(t_ds->pwplan, n, [&](int64_t* leaves) {
+        std::vector<int> plan = dfmi_pairwise_plan((int)n);
+        *leaves = plan[0];
+        return plan;
+      }, &pb))
+    return rc;
+  *out = (const int*)pb->p;
+  if (n_leaves) *n_leaves = pb->aux;
   return DFMI_OK;
 }
 
@@ -376,54 +449,48 @@ uint64_t bits(double v) {
 
 // Basis table for the fold kernel: row c < ndata = cos(fl((c+1) w0) p), row
 // ndata + c = sin(...), p < L. fit.py:55-64 forms the angle as ((n+1)*w0)*t.
-int basis_table(int dev, int L, int ndata, double w0, hipStream_t st, const double** out) {
-  auto key = std::make_tuple(L, ndata, bits(w0));
-  DevBuf& b = t_ds->basis[key];
-  if (!b.p) {
-    std::vector<double> h((size_t)2 * ndata * L);
-    for (int c = 0; c < ndata; ++c) {
-      const double wh = (double)(c + 1) * w0;
-      for (int p = 0; p < L; ++p) {
-        const double ang = wh * (double)p;
-        h[(size_t)c * L + p] = cos(ang);
-        h[(size_t)(ndata + c) * L + p] = sin(ang);
-      }
-    }
-    HIPCHK(hipMalloc(&b.p, h.size() * 8));
-    b.n = h.size() * 8;
-    HIPCHK(hipMemcpy(b.p, h.data(), b.n, hipMemcpyHostToDevice));
-  }
-  (void)st;
-  *out = (const double*)b.p;
+int basis_table(int L, int ndata, double w0, const double** out) {
+  const DevBuf* b;
+  if (int rc = cached_upload(t_ds->basis, std::make_tuple(L, ndata, bits(w0)), [&](int64_t*) {
+        std::vector<double> h((size_t)2 * ndata * L);
+        for (int c = 0; c < ndata; ++c) {
+          const double wh = (double)(c + 1) * w0;
+          for (int p = 0; p < L; ++p) {
+            const double ang = wh * (double)p;
+            h[(size_t)c * L + p] = cos(ang);
+            h[(size_t)(ndata + c) * L + p] = sin(ang);
+          }
+        }
+        return h;
+      }, &b))
+    return rc;
+  *out = (const double*)b->p;
   return DFMI_OK;
 }
 
 // The basis for demod_wide_kernel: pairs (T[o][p], T[o][p+1]) at [(p/2)·64·no + o] for
 // p = 0..L/2 (zero beyond), o over [cos rows | sin rows | ones (dc) | zeros up to 64·no]; the
 // values are basis_table's.
-int basis_table_wide(int dev, int L, int ndata, double w0, int no, const double** out) {
-  auto key = std::make_tuple(L, -(ndata * 8 + no), bits(w0));
-  DevBuf& b = t_ds->basis[key];
-  if (!b.p) {
-    const int w = 64 * no;
-    const int npp = (L / 2 + 2) / 2;
-    std::vector<double> h((size_t)npp * w * 2, 0.0);
-    auto put = [&](int o, int p, double v) { h[((size_t)(p / 2) * w + o) * 2 + (p & 1)] = v; };
-    for (int c = 0; c < ndata; ++c) {
-      const double wh = (double)(c + 1) * w0;
-      for (int p = 0; p <= L / 2; ++p) {
-        const double ang = wh * (double)p;
-        put(c, p, cos(ang));
-        put(ndata + c, p, sin(ang));
-      }
-    }
-    for (int p = 0; p <= L / 2; ++p) put(2 * ndata, p, 1.0);
-    HIPCHK(hipMalloc(&b.p, h.size() * 8));
-    b.n = h.size() * 8;
-    HIPCHK(hipMemcpy(b.p, h.data(), b.n, hipMemcpyHostToDevice));
-  }
-  (void)dev;
-  *out = (const double*)b.p;
+int basis_table_wide(int L, int ndata, double w0, int no, const double** out) {
+  const DevBuf* b;
+  if (int rc = cached_upload(t_ds->basis, std::make_tuple(L, -(ndata * 8 + no), bits(w0)), [&](int64_t*) {
+        const int w = 64 * no;
+        const int npp = (L / 2 + 2) / 2;
+        std::vector<double> h((size_t)npp * w * 2, 0.0);
+        auto put = [&](int o, int p, double v) { h[((size_t)(p / 2) * w + o) * 2 + (p & 1)] = v; };
+        for (int c = 0; c < ndata; ++c) {
+          const double wh = (double)(c + 1) * w0;
+          for (int p = 0; p <= L / 2; ++p) {
+            const double ang = wh * (double)p;
+            put(c, p, cos(ang));
+            put(ndata + c, p, sin(ang));
+          }
+        }
+        for (int p = 0; p <= L / 2; ++p) put(2 * ndata, p, 1.0);
+        return h;
+      }, &b))
+    return rc;
+  *out = (const double*)b->p;
   return DFMI_OK;
 }
 
@@ -436,25 +503,26 @@ void grid_geometry(const dfmi_lm_config& c, int* n, double* delta) {
   *delta = (c.m_grid_min + c.m_grid_step) - c.m_grid_min;
 }
 
-int grid_table(int dev, int ndata, const dfmi_lm_config& c, const double** out) {
-  auto key = std::make_tuple(ndata, bits(c.m_grid_min), bits(c.m_grid_max), bits(c.m_grid_step));
-  DevBuf& b = t_ds->gridtab[key];
-  if (!b.p) {
-    int n;
-    double delta;
-    grid_geometry(c, &n, &delta);
-    std::vector<double> h((size_t)(n > 0 ? n : 1) * ndata, 0.0);
-    std::vector<double> row(ndata + 2);
-    for (int g = 0; g < n; ++g) {
-      const double mtry = c.m_grid_min + (double)g * delta;
-      dfmi_bessel_table(mtry, ndata, row.data());
-      for (int i = 0; i < ndata; ++i) h[(size_t)g * ndata + i] = row[i + 1];
-    }
-    HIPCHK(hipMalloc(&b.p, h.size() * 8));
-    b.n = h.size() * 8;
-    HIPCHK(hipMemcpy(b.p, h.data(), b.n, hipMemcpyHostToDevice));
-  }
-  *out = (const double*)b.p;
+int grid_table(int ndata, const dfmi_lm_config& c, const double** out) {
+  const DevBuf* b;
+  if (int rc = cached_upload(
+          t_ds->gridtab, std::make_tuple(ndata, bits(c.m_grid_min), bits(c.m_grid_max), bits(c.m_grid_step)),
+          [&](int64_t*) {
+            int n;
+            double delta;
+            grid_geometry(c, &n, &delta);
+            std::vector<double> h((size_t)(n > 0 ? n : 1) * ndata, 0.0);
+            std::vector<double> row(ndata + 2);
+            for (int g = 0; g < n; ++g) {
+              const double mtry = c.m_grid_min + (double)g * delta;
+              dfmi_bessel_table(mtry, ndata, row.data());
+              for (int i = 0; i < ndata; ++i) h[(size_t)g * ndata + i] = row[i + 1];
+            }
+            return h;
+          },
+          &b))
+    return rc;
+  *out = (const double*)b->p;
   return DFMI_OK;
 }
 
@@ -655,14 +723,13 @@ bool wide_geometry(bool vec2, int L, int ndata) {
 
 template <int NO, int KSEG, typename XT>
 int launch_wide_t(const XT* x, int64_t nseg, int64_t stride, int R, int L, int ndata, const double* tabT,
-                  double* qi, int64_t qi_ld, double* dc, hipStream_t st, int n_cu) {
+                  double* qi, int64_t qi_ld, double* dc, hipStream_t st) {
   // half-wave contraction where the outputs fit 32 lanes (2·ndata + 1 <= 32)
   const bool half = NO == 1 && 2 * ndata + 1 <= 32 && t_tune.demod_wide_half;
   constexpr int TD = NO >= 4 ? 2 : 8 / NO;  // the kernel's default basis pairs in flight
   auto kern = half ? dfmi::demod_wide_kernel<NO, KSEG, DFMI_WIDE_LOADS, 4, (NO == 1 && KSEG % 2 == 0) ? 1 : 0, TD, XT>
                    : dfmi::demod_wide_kernel<NO, KSEG, DFMI_WIDE_LOADS, 4, 0, TD, XT>;
   const size_t lds = (size_t)dfmi::kWavesPerBlock * KSEG * dfmi::wide_set(L, NO, KSEG) * sizeof(double);
-  (void)n_cu;
   const int64_t per_block = (int64_t)dfmi::kWavesPerBlock * KSEG;
   const int64_t grid = (nseg + per_block - 1) / per_block;  // one group of KSEG segments per wave
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(dfmi::kBlockThreads), lds, st, x, nseg, stride, R, L, ndata,
@@ -674,11 +741,11 @@ int launch_wide_t(const XT* x, int64_t nseg, int64_t stride, int R, int L, int n
 }
 
 template <typename XT>
-int launch_wide(int dev, const XT* x, int64_t nseg, int64_t stride, int R, int L, int ndata, double w0,
-                double* qi, int64_t qi_ld, double* dc, hipStream_t st, int n_cu) {
+int launch_wide(const XT* x, int64_t nseg, int64_t stride, int R, int L, int ndata, double w0,
+                double* qi, int64_t qi_ld, double* dc, hipStream_t st) {
   const int no = wide_no(ndata);
   const double* tabT = nullptr;
-  if (int rc = basis_table_wide(dev, L, ndata, w0, no, &tabT)) return rc;
+  if (int rc = basis_table_wide(L, ndata, w0, no, &tabT)) return rc;
   // KSEG 8: level with 4 at R = 4000 (0.578 / 0.576 ms at ndata 30, r05t-x), ahead at 62 (0.631 /
   // 0.617) and for short segments, where the contraction dominates (R = 200, ndata 10: 0.768 /
   // 0.684 ms; R = 400: 0.471 / 0.423; profiles/r05/short_segments_split.jsonl); fewer where the
@@ -686,9 +753,9 @@ int launch_wide(int dev, const XT* x, int64_t nseg, int64_t stride, int R, int L
   const int k = wide_kseg(L, ndata);
   if (k == 0) return fail(DFMI_ERR_UNSUPPORTED, "demod_wide_kernel: LDS per workgroup too small");
 #define DFMI_WIDE(NO_)                                                                                   \
-  return k == 8 ? launch_wide_t<NO_, 8>(x, nseg, stride, R, L, ndata, tabT, qi, qi_ld, dc, st, n_cu)      \
-         : k == 4 ? launch_wide_t<NO_, 4>(x, nseg, stride, R, L, ndata, tabT, qi, qi_ld, dc, st, n_cu)    \
-                  : launch_wide_t<NO_, 2>(x, nseg, stride, R, L, ndata, tabT, qi, qi_ld, dc, st, n_cu)
+  return k == 8 ? launch_wide_t<NO_, 8>(x, nseg, stride, R, L, ndata, tabT, qi, qi_ld, dc, st)      \
+         : k == 4 ? launch_wide_t<NO_, 4>(x, nseg, stride, R, L, ndata, tabT, qi, qi_ld, dc, st)    \
+                  : launch_wide_t<NO_, 2>(x, nseg, stride, R, L, ndata, tabT, qi, qi_ld, dc, st)
   if (no == 1) DFMI_WIDE(1);
   if (no == 2) DFMI_WIDE(2);
   DFMI_WIDE(4);
@@ -707,21 +774,31 @@ bool bins_applicable(bool vec2, int L, int ndata, size_t lds_cap) {
   return t_tune.demod_kernel == 1 && bins_geometry(vec2, L, ndata, lds_cap, dfmi::kWavesPerBlock);
 }
 
+// Period slots of 128 samples (nslot = ceil(L / 128) <= 8) -> the MS template argument of the
+// LDS bin kernels (bin, fused seed + bin, seed): 2, 4 or 8. with_ms calls f with MS as a
+// std::integral_constant, so each caller names only the instances it launches.
+int ms_of(int nslot) { return nslot <= 2 ? 2 : nslot <= 4 ? 4 : 8; }
+
+template <typename F>
+auto with_ms(int nslot, F f) {
+  switch (ms_of(nslot)) {
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    default: return f(std::integral_constant<int, 8>{});
+  }
+}
+
 // Returns 1 if the bin kernel does not apply.
 template <typename XT>
 int try_bins(const XT* x, int64_t nseg, int64_t stride, int R, int L, int ndata, const double* tab, double* qi,
              int64_t qi_ld, double* dc, hipStream_t st, int n_cu, bool vec2, size_t lds_cap, bool rows) {
   if (!bins_applicable(vec2, L, ndata, lds_cap)) return 1;
   const size_t lds = ((size_t)2 * ndata * L + (size_t)dfmi::kWavesPerBlock * L) * sizeof(double);
-  const int nslot = (L + 127) / 128;
-  if (rows) {
-    if (nslot <= 2) return launch_bins_t<2, true>(x, nseg, stride, R, L, ndata, tab, qi, qi_ld, dc, st, n_cu, lds);
-    if (nslot <= 4) return launch_bins_t<4, true>(x, nseg, stride, R, L, ndata, tab, qi, qi_ld, dc, st, n_cu, lds);
-    return launch_bins_t<8, true>(x, nseg, stride, R, L, ndata, tab, qi, qi_ld, dc, st, n_cu, lds);
-  }
-  if (nslot <= 2) return launch_bins_t<2, false>(x, nseg, stride, R, L, ndata, tab, qi, qi_ld, dc, st, n_cu, lds);
-  if (nslot <= 4) return launch_bins_t<4, false>(x, nseg, stride, R, L, ndata, tab, qi, qi_ld, dc, st, n_cu, lds);
-  return launch_bins_t<8, false>(x, nseg, stride, R, L, ndata, tab, qi, qi_ld, dc, st, n_cu, lds);
+  return with_ms((L + 127) / 128, [&](auto ms) {
+    constexpr int MS = decltype(ms)::value;
+    return rows ? launch_bins_t<MS, true>(x, nseg, stride, R, L, ndata, tab, qi, qi_ld, dc, st, n_cu, lds)
+                : launch_bins_t<MS, false>(x, nseg, stride, R, L, ndata, tab, qi, qi_ld, dc, st, n_cu, lds);
+  });
 }
 
 // Sample pairs loadable as one vector: rows aligned to two samples (16 B for double, 8 B for
@@ -736,11 +813,11 @@ bool vec2_ok(const XT* x, int64_t stride, int L) {
 // stride, 16-B aligned), followed by the double branch on it; dfmi_last_demod_kernel then
 // ends in " [f32 widened]".
 template <typename XT>
-int widen_rows(int dev, const XT* x, int64_t nseg, int64_t stride, int R, hipStream_t st, const double** out,
+int widen_rows(const XT* x, int64_t nseg, int64_t stride, int R, hipStream_t st, const double** out,
                int64_t* out_stride) {
   const int64_t ws = (int64_t)R + (R & 1);
   void* w = nullptr;
-  if (int rc = workspace(dev, "x_widen", (size_t)nseg * ws * sizeof(double), &w)) return rc;
+  if (int rc = workspace("x_widen", (size_t)nseg * ws * sizeof(double), &w)) return rc;
   int64_t grid = (nseg * (int64_t)R + 255) / 256;
   if (grid > (int64_t)t_ds->n_cu * 16) grid = (int64_t)t_ds->n_cu * 16;
   hipLaunchKernelGGL(dfmi::widen_rows_kernel<XT>, dim3((unsigned)grid), dim3(256), 0, st, x, nseg, stride, (int64_t)R,
@@ -754,7 +831,7 @@ int widen_rows(int dev, const XT* x, int64_t nseg, int64_t stride, int R, hipStr
 // Whether demod_device can write the row layout (dfmi_qi_row_stride) for this
 // input: only the bin-in-LDS kernel implements it.
 template <typename XT>
-bool rows_supported(int dev, const XT* x, int64_t stride, int R, int ndata, double w0, int period) {
+bool rows_supported(const XT* x, int64_t stride, int R, int ndata, double w0, int period) {
   int L = period;
   if (L == 0) L = detect_period_impl(w0, R, ndata);
   if (L <= 0) return false;
@@ -765,7 +842,7 @@ bool rows_supported(int dev, const XT* x, int64_t stride, int R, int ndata, doub
 // rows = true: write the row layout (qi + s·qi_ld, dfmi_qi_row_stride; dc inside
 // the row, `dc` unused) — callers check rows_supported() first.
 template <typename XT>
-int demod_device(int dev, const XT* x, int64_t nseg, int64_t stride, int R, int ndata, double w0, int period,
+int demod_device(const XT* x, int64_t nseg, int64_t stride, int R, int ndata, double w0, int period,
                  double* qi, int64_t qi_ld, double* dc, hipStream_t st, bool rows = false) {
   if (nseg == 0) return DFMI_OK;
   int L = period;
@@ -780,23 +857,23 @@ int demod_device(int dev, const XT* x, int64_t nseg, int64_t stride, int R, int 
       int ms = 1;
       while (ms < nslot) ms <<= 1;
       const double* tab = nullptr;
-      int rc = basis_table(dev, L, ndata, w0, st, &tab);
+      int rc = basis_table(L, ndata, w0, &tab);
       if (rc) return rc;
       const size_t lds = (size_t)2 * ndata * L * sizeof(double);
       const bool use_lds = lds <= 64 * 1024 && lds <= lds_cap;
       if (!rows && wide_first(ndata, R) && wide_geometry(vec2, L, ndata))
-        return launch_wide(dev, x, nseg, stride, R, L, ndata, w0, qi, qi_ld, dc, st, n_cu);
+        return launch_wide(x, nseg, stride, R, L, ndata, w0, qi, qi_ld, dc, st);
       rc = try_bins(x, nseg, stride, R, L, ndata, tab, qi, qi_ld, dc, st, n_cu, vec2, lds_cap, rows);
       if (rc <= 0) return rc;
       if (rows) return fail(DFMI_ERR_UNSUPPORTED, "row layout needs the bin-in-LDS demodulation kernel");
       if (t_tune.demod_wide && t_tune.demod_kernel == 1 && wide_geometry(vec2, L, ndata))
-        return launch_wide(dev, x, nseg, stride, R, L, ndata, w0, qi, qi_ld, dc, st, n_cu);
+        return launch_wide(x, nseg, stride, R, L, ndata, w0, qi, qi_ld, dc, st);
       // the fold kernel reads doubles: another sample type is widened first, and the branch
       // (VEC from the rows' own pair alignment) is the one a double record of this layout takes
       const double* xd = nullptr;
       int64_t sd = stride;
       if constexpr (std::is_same<XT, double>::value) xd = x;
-      else if ((rc = widen_rows(dev, x, nseg, stride, R, st, &xd, &sd))) return rc;
+      else if ((rc = widen_rows(x, nseg, stride, R, st, &xd, &sd))) return rc;
       if (vec2) {
         rc = use_lds ? launch_fold_ms<2, true>(ms, xd, nseg, sd, R, L, ndata, tab, qi, qi_ld, dc, st, n_cu)
                      : launch_fold_ms<2, false>(ms, xd, nseg, sd, R, L, ndata, tab, qi, qi_ld, dc, st, n_cu);
@@ -812,7 +889,7 @@ int demod_device(int dev, const XT* x, int64_t nseg, int64_t stride, int R, int 
   const double* xd = nullptr;
   int64_t sd = stride;
   if constexpr (std::is_same<XT, double>::value) xd = x;
-  else if (int rc = widen_rows(dev, x, nseg, stride, R, st, &xd, &sd)) return rc;
+  else if (int rc = widen_rows(x, nseg, stride, R, st, &xd, &sd)) return rc;
   // direct kernel
   int64_t need = (nseg + dfmi::kWavesPerBlock - 1) / dfmi::kWavesPerBlock;
   int64_t grid = (int64_t)n_cu * 8;
@@ -824,37 +901,70 @@ int demod_device(int dev, const XT* x, int64_t nseg, int64_t stride, int R, int 
   return DFMI_OK;
 }
 
-// LM kernel selection: the register path (ndata <= 16; the exact-ndata variant with QI
-// in registers for the reference default ndata = 10) or the general path (any ndata,
-// or lm_general = 1). CHAIN: warm-start chains (sequential / n_cores chunks).
+// LM variant selection, stated once for the one-lane kernels (lm_kernel) and the lambda ladder
+// (lm_ladder): the register path (ndata <= 16; the exact-ndata variant with QI in registers for
+// the reference default ndata = 10) or the general path (any ndata, or lm_general = 1).
 // nd_sel: ndata, or 1000 for the literal general path (lm_general = 1); beyond 16 harmonics
-// the many-harmonic path (lm.h kWideNd) on component-major QI, "lm_wide" = 0 the literal one.
+// the many-harmonic path (lm.h kWideNd / kWideNdF) on component-major QI, "lm_wide" = 0 the
+// literal one. The row layout never takes the many-harmonic path (it stops at 16 harmonics'
+// rows; beyond, the general path reads them).
+enum class LmVar { Nd10, Nd12, Nd16, Wide, WideFused, General };
+
+LmVar lm_variant(int nd_sel, bool rows) {
+  if (nd_sel == 10) return LmVar::Nd10;
+  if (nd_sel <= 12) return LmVar::Nd12;
+  if (nd_sel <= 16) return LmVar::Nd16;
+  if (rows || nd_sel >= 1000 || !t_tune.lm_wide) return LmVar::General;
+  return t_tune.lm_wide_fused ? LmVar::WideFused : LmVar::Wide;
+}
+
+// The one-lane kernel of a variant. CHAIN: warm-start chains (sequential / n_cores chunks), which
+// have no one-walk (fused) many-harmonic instance: WideFused runs Wide there.
 template <bool CHAIN, bool ROWS>
-auto lm_kernel(int nd_sel) {
+auto lm_kernel(LmVar v) {
   constexpr int kNd10 = dfmi::kExactNd | 10;
-  const bool wide = nd_sel > 16 && nd_sel < 1000 && t_tune.lm_wide && !ROWS;
   if constexpr (CHAIN) {
-    return nd_sel == 10   ? dfmi::lm_chunks_kernel<kNd10, true>
-           : nd_sel <= 12 ? dfmi::lm_chunks_kernel<12, true>
-           : nd_sel <= 16 ? dfmi::lm_chunks_kernel<16, true>
-           : wide         ? dfmi::lm_chunks_kernel<dfmi::kWideNd, true>
-                          : dfmi::lm_chunks_kernel<0, true>;
+    switch (v) {
+      case LmVar::Nd10: return dfmi::lm_chunks_kernel<kNd10, true>;
+      case LmVar::Nd12: return dfmi::lm_chunks_kernel<12, true>;
+      case LmVar::Nd16: return dfmi::lm_chunks_kernel<16, true>;
+      case LmVar::Wide:
+      case LmVar::WideFused: return dfmi::lm_chunks_kernel<dfmi::kWideNd, true>;
+      default: return dfmi::lm_chunks_kernel<0, true>;
+    }
   } else {
-    return nd_sel == 10   ? dfmi::lm_chunks_kernel<kNd10, false, ROWS, true>
-           : nd_sel <= 12 ? dfmi::lm_chunks_kernel<12, false, ROWS>
-           : nd_sel <= 16 ? dfmi::lm_chunks_kernel<16, false, ROWS>
-           : wide && t_tune.lm_wide_fused ? dfmi::lm_chunks_kernel<dfmi::kWideNdF, false, false>
-           : wide                         ? dfmi::lm_chunks_kernel<dfmi::kWideNd, false, false>
-                                          : dfmi::lm_chunks_kernel<0, false, ROWS>;
+    switch (v) {
+      case LmVar::Nd10: return dfmi::lm_chunks_kernel<kNd10, false, ROWS, true>;
+      case LmVar::Nd12: return dfmi::lm_chunks_kernel<12, false, ROWS>;
+      case LmVar::Nd16: return dfmi::lm_chunks_kernel<16, false, ROWS>;
+      case LmVar::WideFused: return dfmi::lm_chunks_kernel<dfmi::kWideNdF, false, false>;
+      case LmVar::Wide: return dfmi::lm_chunks_kernel<dfmi::kWideNd, false, false>;
+      default: return dfmi::lm_chunks_kernel<0, false, ROWS>;
+    }
   }
 }
 
-int lm_device(int dev, const double* qi, int64_t qi_ld, int ndata, int64_t nrec, int64_t nbuf, int64_t first,
+// The ladder kernel of a variant (kLadderLanes lanes per item). Beyond 16 harmonics the
+// many-harmonic evaluation as in the one-lane kernels (same bits as lm_chunks_kernel<kWideNd /
+// kWideNdF>: the ladder only tries the rungs in parallel).
+template <bool CHAIN, bool ROWS>
+auto lm_ladder(LmVar v) {
+  constexpr int kNd10 = dfmi::kExactNd | 10;
+  switch (v) {
+    case LmVar::Nd10: return dfmi::lm_ladder_kernel<kNd10, CHAIN, ROWS>;
+    case LmVar::Nd12: return dfmi::lm_ladder_kernel<12, CHAIN, ROWS>;
+    case LmVar::Nd16: return dfmi::lm_ladder_kernel<16, CHAIN, ROWS>;
+    case LmVar::WideFused: return dfmi::lm_ladder_kernel<dfmi::kWideNdF, CHAIN, false>;
+    case LmVar::Wide: return dfmi::lm_ladder_kernel<dfmi::kWideNd, CHAIN, false>;
+    default: return dfmi::lm_ladder_kernel<0, CHAIN, ROWS>;
+  }
+}
+
+int lm_device(const double* qi, int64_t qi_ld, int ndata, int64_t nrec, int64_t nbuf, int64_t first,
               int64_t nitems, int64_t nchunk, const double* guess_dev, int64_t g_rec, int64_t g_comp,
               const double* guess_host /* nrec*4, used when nrec <= 8 and guess_dev == null */,
               const dfmi::LMConst& c, const double* jtab, double* out, int64_t out_ld, int32_t* status,
               hipStream_t st, bool rows = false) {
-  (void)dev;
   if (nrec == 0 || nitems == 0) return DFMI_OK;
   if (nchunk < 1) nchunk = 1;
   if (nchunk > nitems) nchunk = nitems;  // np.array_split chunks beyond nitems are empty
@@ -873,33 +983,15 @@ int lm_device(int dev, const double* qi, int64_t qi_ld, int ndata, int64_t nrec,
   const bool chain = nitems > nchunk;
   const int nd_sel = t_tune.lm_general ? 1000 : ndata;
   if (rows && chain) return fail(DFMI_ERR_ARG, "row layout: chunk size 1 only");
+  const LmVar var = lm_variant(nd_sel, rows);
+  const bool wide = var == LmVar::Wide || var == LmVar::WideFused;
   // latency-bound launches (few chains or segments: at most ~2 ladder waves per SIMD):
   // the parallel lambda ladder, kLadderLanes lanes per item (lm.h lm_ladder_kernel)
   if (t_tune.lm_ladder && lanes <= (int64_t)t_tune.lm_ladder * t_ds->n_cu) {
-    constexpr int kNd10 = dfmi::kExactNd | 10;
-    using LK = void (*)(const double*, int64_t, int, int64_t, int64_t, int64_t, int64_t, int64_t, const double*,
-                        int64_t, int64_t, dfmi::GuessInline, int, const double*, dfmi::LMConst, double*, int64_t,
-                        int32_t*);
-    LK lk;
-    // beyond 16 harmonics the many-harmonic evaluation as in the one-lane kernels (same bits as
-    // lm_chunks_kernel<kWideNd / kWideNdF>: the ladder only tries the rungs in parallel)
-    const bool wide = nd_sel > 16 && nd_sel < 1000 && t_tune.lm_wide;
-    if (rows)
-      lk = nd_sel == 10 ? dfmi::lm_ladder_kernel<kNd10, false, true> : nd_sel <= 12 ? dfmi::lm_ladder_kernel<12, false, true>
-           : nd_sel <= 16 ? dfmi::lm_ladder_kernel<16, false, true> : dfmi::lm_ladder_kernel<0, false, true>;
-    else if (chain)
-      lk = nd_sel == 10 ? dfmi::lm_ladder_kernel<kNd10, true, false> : nd_sel <= 12 ? dfmi::lm_ladder_kernel<12, true, false>
-           : nd_sel <= 16 ? dfmi::lm_ladder_kernel<16, true, false>
-           : wide && t_tune.lm_wide_fused ? dfmi::lm_ladder_kernel<dfmi::kWideNdF, true, false>
-           : wide ? dfmi::lm_ladder_kernel<dfmi::kWideNd, true, false> : dfmi::lm_ladder_kernel<0, true, false>;
-    else
-      lk = nd_sel == 10 ? dfmi::lm_ladder_kernel<kNd10, false, false> : nd_sel <= 12 ? dfmi::lm_ladder_kernel<12, false, false>
-           : nd_sel <= 16 ? dfmi::lm_ladder_kernel<16, false, false>
-           : wide && t_tune.lm_wide_fused ? dfmi::lm_ladder_kernel<dfmi::kWideNdF, false, false>
-           : wide ? dfmi::lm_ladder_kernel<dfmi::kWideNd, false, false> : dfmi::lm_ladder_kernel<0, false, false>;
+    auto lk = chain ? lm_ladder<true, false>(var) : rows ? lm_ladder<false, true>(var) : lm_ladder<false, false>(var);
     // beyond 16 harmonics, while at most lm_ladder_split x CUs items: one wave per item, its 64
     // lanes 8 rungs x 8 harmonic shares (lm.h PartFullEval, as the seed)
-    const bool wsplit = !rows && wide && t_tune.lm_wide_fused && t_tune.lm_ladder_split &&
+    const bool wsplit = var == LmVar::WideFused && t_tune.lm_ladder_split &&
                         lanes <= (int64_t)t_tune.lm_ladder_split * t_ds->n_cu;
     if (wsplit) lk = chain ? dfmi::lm_ladder_kernel<dfmi::kWideNdF, true, false, 64>
                            : dfmi::lm_ladder_kernel<dfmi::kWideNdF, false, false, 64>;
@@ -910,8 +1002,7 @@ int lm_device(int dev, const double* qi, int64_t qi_ld, int ndata, int64_t nrec,
     return DFMI_OK;
   }
   size_t lds = 0;
-  auto kern = chain ? lm_kernel<true, false>(nd_sel) : rows ? lm_kernel<false, true>(nd_sel)
-                                                            : lm_kernel<false, false>(nd_sel);
+  auto kern = chain ? lm_kernel<true, false>(var) : rows ? lm_kernel<false, true>(var) : lm_kernel<false, false>(var);
   if (rows && nd_sel <= 16) lds = (size_t)qi_ld * 65 * sizeof(double);  // the wave's rows, transposed
   // the general path's one-pass Bessel walk: the lane's recurrence values in LDS, while 7
   // waves per CU still fit (ndata + 2 <= 45): ndata 40 0.276 -> 0.264 ms per 100k; at 62 (5
@@ -919,7 +1010,7 @@ int lm_device(int dev, const double* qi, int64_t qi_ld, int ndata, int64_t nrec,
   // many harmonics, P lanes per segment (lm.h lm_split_kernel: QI in a per-wave LDS tile of
   // 64 / P segments) from "lm_split_from" harmonics on ("lm_split" = P, 0 = never)
   const int sp = t_tune.lm_split;
-  if (!chain && !rows && nd_sel > 16 && nd_sel < 1000 && t_tune.lm_wide && sp > 1 && ndata >= t_tune.lm_split_from &&
+  if (!chain && wide && sp > 1 && ndata >= t_tune.lm_split_from &&
       (size_t)2 * ndata * (64 / sp) * sizeof(double) <= t_ds->lds_per_block) {
     const size_t slds = (size_t)2 * ndata * (64 / sp) * sizeof(double);
     const int64_t sgrid = (nrec * nitems + 64 / sp - 1) / (64 / sp);
@@ -931,14 +1022,14 @@ int lm_device(int dev, const double* qi, int64_t qi_ld, int ndata, int64_t nrec,
   }
   // many harmonics with QI staged in LDS per lane (lm.h QLds) while 2 ndata x 64 x 8 B per wave
   // leaves 8 waves per CU ("lm_wide_lds": the largest ndata staged, default 20 = 20 KB)
-  if (!chain && !rows && nd_sel > 16 && nd_sel < 1000 && t_tune.lm_wide && ndata <= t_tune.lm_wide_lds &&
+  if (!chain && wide && ndata <= t_tune.lm_wide_lds &&
       (size_t)2 * ndata * 64 * sizeof(double) <= t_ds->lds_per_block) {
     // (split trials here: the one-walk form measured slower with the QI in LDS, 0.078 against
     // 0.073 ms at ndata 20, profiles/r06/ndata_sweep_fused.jsonl)
     kern = dfmi::lm_chunks_kernel<dfmi::kWideNd, false, false, true>;
     lds = (size_t)2 * ndata * 64 * sizeof(double);
   }
-  if (!chain && !rows && nd_sel > 16 && !(t_tune.lm_wide && nd_sel < 1000) && t_tune.lm_onepass &&
+  if (!chain && !rows && var == LmVar::General && t_tune.lm_onepass &&
       (t_tune.lm_onepass == 2 || (size_t)64 * (ndata + 2) * 8 * 7 <= t_ds->lds_per_block)) {
     kern = dfmi::lm_chunks_kernel<0, false, false, false, true>;
     lds = (size_t)64 * (ndata + 2) * sizeof(double);
@@ -953,7 +1044,7 @@ int lm_device(int dev, const double* qi, int64_t qi_ld, int ndata, int64_t nrec,
 // Fused seed + bulk demodulation (seed.h demod_seed_bins_kernel) on one stream.
 // Returns 1 when it does not apply (caller uses the two-kernel path).
 template <typename XT>
-int fused_seed_demod(int dev, const XT* x, int64_t nrec, int64_t nbuf, int R, int ndata, int L,
+int fused_seed_demod(const XT* x, int64_t nrec, int64_t nbuf, int R, int ndata, int L,
                      const double* tab, double* rows, int64_t qs, const double* gdev, const dfmi::GuessInline& ginl,
                      const double* jtab, const dfmi::LMConst& c, double* out, int64_t out_ld, int32_t* fitok,
                      hipStream_t st) {
@@ -963,18 +1054,17 @@ int fused_seed_demod(int dev, const XT* x, int64_t nrec, int64_t nbuf, int R, in
   using K = void (*)(const XT*, int64_t, int64_t, int64_t, int, int, int, const double*, double*, int64_t,
                      const double*, dfmi::GuessInline, int, const double*, dfmi::LMConst, double*, int64_t, int64_t,
                      int32_t*, uint64_t*);
-  const bool pf = nslot <= 2 && ndata <= 12;  // bins_segment's prefetch (bulk path, MS 2)
-  K kern;
+  // the build's loads in flight / prefetched chunks (bins_segment's prefetch: bulk path) at MS 2
+  // with up to 12 harmonics only; every other instance 8 loads, no prefetch
+  const bool pf = ms_of(nslot) == 2 && ndata <= 12;
   const size_t lds = ((size_t)2 * ndata * L + (size_t)dfmi::kWavesPerBlock * L) * sizeof(double) +
-                     (nslot <= 2 && ndata <= 12 ? DFMI_BINS_LDS_PAD : 0);
-  if (ndata <= 12)
-    kern = nslot <= 2   ? dfmi::demod_seed_bins_kernel<2, 12, DFMI_BINS_PFN, DFMI_BINS_LOADS, XT>
-           : nslot <= 4 ? dfmi::demod_seed_bins_kernel<4, 12, 0, 8, XT>
-                        : dfmi::demod_seed_bins_kernel<8, 12, 0, 8, XT>;
-  else
-    kern = nslot <= 2   ? dfmi::demod_seed_bins_kernel<2, 16, 0, 8, XT>
-           : nslot <= 4 ? dfmi::demod_seed_bins_kernel<4, 16, 0, 8, XT>
-                        : dfmi::demod_seed_bins_kernel<8, 16, 0, 8, XT>;
+                     (pf ? DFMI_BINS_LDS_PAD : 0);
+  const K kern = with_ms(nslot, [&](auto ms) -> K {
+    constexpr int MS = decltype(ms)::value;
+    if (ndata <= 12)
+      return dfmi::demod_seed_bins_kernel<MS, 12, MS == 2 ? DFMI_BINS_PFN : 0, MS == 2 ? DFMI_BINS_LOADS : 8, XT>;
+    return dfmi::demod_seed_bins_kernel<MS, 16, 0, 8, XT>;
+  });
   int per_cu = 0;
   if (int orc = occupancy(kern, dfmi::kBlockThreads, lds, &per_cu)) return orc;
   if (per_cu < 1) per_cu = 1;
@@ -994,10 +1084,9 @@ int fused_seed_demod(int dev, const XT* x, int64_t nrec, int64_t nbuf, int R, in
   HIPCHK(hipGetLastError());
   // the template arguments of the instance launched (loads in flight / prefetched chunks
   // from the build's macros, so A/B builds report their own geometry)
-  const bool geo = nslot <= 2 && ndata <= 12;
-  g_last_demod = "demod_seed_bins_kernel<" + std::to_string(nslot <= 2 ? 2 : nslot <= 4 ? 4 : 8) + "," +
-                 std::to_string(ndata <= 12 ? 12 : 16) + "," + std::to_string(geo ? DFMI_BINS_PFN : 0) + "," +
-                 std::to_string(geo ? DFMI_BINS_LOADS : 8) + ">" +
+  g_last_demod = "demod_seed_bins_kernel<" + std::to_string(ms_of(nslot)) + "," +
+                 std::to_string(ndata <= 12 ? 12 : 16) + "," + std::to_string(pf ? DFMI_BINS_PFN : 0) + "," +
+                 std::to_string(pf ? DFMI_BINS_LOADS : 8) + ">" +
                  (pf && (R >> 7) >= DFMI_BINS_PFN ? " (prefetch " + std::to_string(DFMI_BINS_PFN) + ")" : "") +
                  xt_tag<XT>();
   return DFMI_OK;
@@ -1009,32 +1098,28 @@ int fused_seed_demod(int dev, const XT* x, int64_t nrec, int64_t nbuf, int R, in
 // fold (seed_bins_kernel) wherever its geometry applies — the fused kernel's seed fold,
 // so both paths give the same bits — the global fold / direct kernel otherwise.
 template <typename XT>
-int seed_launch(int dev, const XT* x, int64_t nrec, int64_t rec_stride, int R, int ndata, double w0, int L,
+int seed_launch(const XT* x, int64_t nrec, int64_t rec_stride, int R, int ndata, double w0, int L,
                 const double* gdev, const dfmi::GuessInline& ginl, const double* jtab, const dfmi::LMConst& c,
                 double* out, int64_t out_ld, int64_t nbuf, int32_t* fitok, hipStream_t sst, bool seed_dc) {
   int rc;
   if (L > 64 * 16) L = 0;  // no table: the direct kernel's per-sample sincos
   const double* tab = nullptr;
-  if (L > 0 && (rc = basis_table(dev, L, ndata, w0, sst, &tab))) return rc;
+  if (L > 0 && (rc = basis_table(L, ndata, w0, &tab))) return rc;
   const bool vec2 = L > 0 && vec2_ok(x, nrec > 1 ? rec_stride : 0, L);
   const size_t blds = ((size_t)2 * ndata * L + L + dfmi_row_stride(ndata)) * sizeof(double);
   if (L > 0 && bins_geometry(vec2, L, ndata, t_ds->lds_per_block, 1) && blds <= t_ds->lds_per_block) {
-    const int nslot = (L + 127) / 128;
-    auto sk = ndata <= 12   ? (nslot <= 2   ? dfmi::seed_bins_kernel<12, 2, XT>
-                               : nslot <= 4 ? dfmi::seed_bins_kernel<12, 4, XT>
-                                            : dfmi::seed_bins_kernel<12, 8, XT>)
-              : ndata <= 16 ? (nslot <= 2   ? dfmi::seed_bins_kernel<16, 2, XT>
-                               : nslot <= 4 ? dfmi::seed_bins_kernel<16, 4, XT>
-                                            : dfmi::seed_bins_kernel<16, 8, XT>)
-                            : (nslot <= 2   ? dfmi::seed_bins_kernel<0, 2, XT>
-                               : nslot <= 4 ? dfmi::seed_bins_kernel<0, 4, XT>
-                                            : dfmi::seed_bins_kernel<0, 8, XT>);
+    auto sk = with_ms((L + 127) / 128, [&](auto ms) {
+      constexpr int MS = decltype(ms)::value;
+      return ndata <= 12   ? dfmi::seed_bins_kernel<12, MS, XT>
+             : ndata <= 16 ? dfmi::seed_bins_kernel<16, MS, XT>
+                           : dfmi::seed_bins_kernel<0, MS, XT>;
+    });
     hipLaunchKernelGGL(sk, dim3((unsigned)nrec), dim3(64), blds, sst, x, rec_stride, R, L, ndata, tab, gdev, ginl,
                        gdev ? 0 : 1, jtab, c, out, out_ld, nbuf, fitok, t_ds->probe, seed_dc ? 1 : 0);
   } else {
     void *qs, *ds_;
-    if ((rc = workspace(dev, "qi_seed", (size_t)2 * ndata * nrec * 8, &qs))) return rc;
-    if ((rc = workspace(dev, "dc_seed", (size_t)nrec * 8, &ds_))) return rc;
+    if ((rc = workspace("qi_seed", (size_t)2 * ndata * nrec * 8, &qs))) return rc;
+    if ((rc = workspace("dc_seed", (size_t)nrec * 8, &ds_))) return rc;
     constexpr int SF = dfmi::kSeedFlat;
     auto sk = ndata <= 12 ? dfmi::seed_kernel<12, SF, XT> : ndata <= 16 ? dfmi::seed_kernel<16, SF, XT>
               : t_tune.lm_wide ? (t_tune.seed_wave_split ? dfmi::seed_kernel<dfmi::kWideNdF, 3, XT>
@@ -1048,7 +1133,7 @@ int seed_launch(int dev, const XT* x, int64_t nrec, int64_t rec_stride, int R, i
     int no = 0;
     if (L > 0 && wide_geometry(vec2, L, ndata)) {
       no = wide_no(ndata);
-      if ((rc = basis_table_wide(dev, L, ndata, w0, no, &tabT))) return rc;
+      if ((rc = basis_table_wide(L, ndata, w0, no, &tabT))) return rc;
     }
     const size_t lds = tabT ? (size_t)(L + 4) * sizeof(double) : 0;
     hipLaunchKernelGGL(sk, dim3((unsigned)nrec), dim3(64), lds, sst, x, rec_stride, R, L, ndata, w0, tab,
@@ -1060,7 +1145,7 @@ int seed_launch(int dev, const XT* x, int64_t nrec, int64_t rec_stride, int R, i
 }
 
 template <typename XT>
-int nls_record_device(int dev, const XT* x, int64_t nrec, int64_t rec_stride, int64_t nbuf, int R, int ndata,
+int nls_record_device(const XT* x, int64_t nrec, int64_t rec_stride, int64_t nbuf, int R, int ndata,
                       double w0, int period, const double* init_guess_host, int parallel, int64_t nchunk,
                       const dfmi_lm_config& cfg, const dfmi::LMConst& c, double* out, int32_t* fitok,
                       hipStream_t st) {
@@ -1068,7 +1153,7 @@ int nls_record_device(int dev, const XT* x, int64_t nrec, int64_t rec_stride, in
   if (nseg == 0) return DFMI_OK;
   DeviceState& ds = *t_ds;
   const double* jtab = nullptr;
-  int rc = grid_table(dev, ndata, cfg, &jtab);
+  int rc = grid_table(ndata, cfg, &jtab);
   if (rc) return rc;
   const int64_t out_ld = nseg;
   double* dc = out + 4 * out_ld;
@@ -1076,7 +1161,7 @@ int nls_record_device(int dev, const XT* x, int64_t nrec, int64_t rec_stride, in
   const double* gdev = nullptr;
   if (nrec > 8) {
     void* gw = nullptr;
-    rc = workspace(dev, "guess", (size_t)nrec * 4 * sizeof(double), &gw);
+    rc = workspace("guess", (size_t)nrec * 4 * sizeof(double), &gw);
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(gw, init_guess_host, (size_t)nrec * 4 * sizeof(double), hipMemcpyHostToDevice, st));
     gdev = (const double*)gw;
@@ -1096,23 +1181,23 @@ int nls_record_device(int dev, const XT* x, int64_t nrec, int64_t rec_stride, in
   const bool even_recs = nrec == 1 || (rec_stride % 2) == 0;
   const bool wide = L > 0 && even_recs && wide_first(ndata, R) && wide_geometry(vec2_ok(x, R, L), L, ndata);
   const bool rows = parallel && (nbuf <= 1 || nchunk >= nbuf - 1) && even_recs && !wide &&
-                    rows_supported(dev, x, R, R, ndata, w0, period);
+                    rows_supported(x, R, R, ndata, w0, period);
   const int64_t qs = rows ? dfmi_row_stride(ndata) : 0;
   if (parallel && rows && (nrec == 1 || rec_stride == nbuf * (int64_t)R) && nbuf > 1) {
     // ONE launch: the seeds (buffer 0 of every record) + the bulk demodulation; the LM
     // follows in stream order
     const double* tab = nullptr;
-    if ((rc = basis_table(dev, L, ndata, w0, st, &tab))) return rc;
+    if ((rc = basis_table(L, ndata, w0, &tab))) return rc;
     void* rw = nullptr;
-    if ((rc = workspace(dev, "qrow", (size_t)qs * nseg * sizeof(double), &rw))) return rc;
+    if ((rc = workspace("qrow", (size_t)qs * nseg * sizeof(double), &rw))) return rc;
     StepMarks sm;
     if ((rc = sm.begin(ds)) || (rc = sm.mark(0, st))) return rc;
-    rc = fused_seed_demod(dev, x, nrec, nbuf, R, ndata, L, tab, (double*)rw, qs, gdev, ginl, jtab, c, out, out_ld,
+    rc = fused_seed_demod(x, nrec, nbuf, R, ndata, L, tab, (double*)rw, qs, gdev, ginl, jtab, c, out, out_ld,
                           fitok, st);
     if (rc < 0) return rc;
     if (rc == 0) {
       if ((rc = sm.mark(1, st))) return rc;
-      rc = lm_device(dev, (double*)rw, qs, ndata, nrec, nbuf, 1, nbuf - 1, nchunk, out, nbuf, out_ld, nullptr, c,
+      rc = lm_device((double*)rw, qs, ndata, nrec, nbuf, 1, nbuf - 1, nchunk, out, nbuf, out_ld, nullptr, c,
                      jtab, out, out_ld, fitok, st, true);
       if (rc) return rc;
       if ((rc = sm.mark(2, st))) return rc;
@@ -1126,7 +1211,7 @@ int nls_record_device(int dev, const XT* x, int64_t nrec, int64_t rec_stride, in
     HIPCHK(hipStreamWaitEvent(ds.side, ds.ev_in, 0));
     // buffer 0's dc: the bulk demodulation writes it on the component-major path (beside the
     // seed, unordered: one writer only); on the row path the LM skips buffer 0, so the seed does
-    if ((rc = seed_launch(dev, x, nrec, rec_stride, R, ndata, w0, L, gdev, ginl, jtab, c, out, out_ld, nbuf, fitok,
+    if ((rc = seed_launch(x, nrec, rec_stride, R, ndata, w0, L, gdev, ginl, jtab, c, out, out_ld, nbuf, fitok,
                           ds.side, rows)))
       return rc;
     HIPCHK(hipEventRecord(ds.ev_seed, ds.side));
@@ -1134,25 +1219,25 @@ int nls_record_device(int dev, const XT* x, int64_t nrec, int64_t rec_stride, in
   double* qi = nullptr;
   {
     void* w = nullptr;
-    if (rows) rc = workspace(dev, "qrow", (size_t)qs * nseg * sizeof(double), &w);
-    else rc = workspace(dev, "qi", (size_t)2 * ndata * nseg * sizeof(double), &w);
+    if (rows) rc = workspace("qrow", (size_t)qs * nseg * sizeof(double), &w);
+    else rc = workspace("qi", (size_t)2 * ndata * nseg * sizeof(double), &w);
     if (rc) return rc;
     qi = (double*)w;
   }
   if (rec_stride == nbuf * (int64_t)R || nrec == 1) {
-    rc = rows ? demod_device(dev, x, nseg, R, R, ndata, w0, period, qi, qs, nullptr, st, true)
-              : demod_device(dev, x, nseg, R, R, ndata, w0, period, qi, nseg, dc, st);
+    rc = rows ? demod_device(x, nseg, R, R, ndata, w0, period, qi, qs, nullptr, st, true)
+              : demod_device(x, nseg, R, R, ndata, w0, period, qi, nseg, dc, st);
   } else {
     for (int64_t r = 0; r < nrec && rc == 0; ++r) {
-      rc = rows ? demod_device(dev, x + r * rec_stride, nbuf, R, R, ndata, w0, period, qi + r * nbuf * qs, qs,
+      rc = rows ? demod_device(x + r * rec_stride, nbuf, R, R, ndata, w0, period, qi + r * nbuf * qs, qs,
                                nullptr, st, true)
-                : demod_device(dev, x + r * rec_stride, nbuf, R, R, ndata, w0, period, qi + r * nbuf, nseg,
+                : demod_device(x + r * rec_stride, nbuf, R, R, ndata, w0, period, qi + r * nbuf, nseg,
                                dc + r * nbuf, st);
     }
   }
   if (rc) return rc;
   if (!parallel) {
-    return lm_device(dev, qi, nseg, ndata, nrec, nbuf, 0, nbuf, 1, gdev, 4, 1, init_guess_host, c, jtab, out, out_ld,
+    return lm_device(qi, nseg, ndata, nrec, nbuf, 0, nbuf, 1, gdev, 4, 1, init_guess_host, c, jtab, out, out_ld,
                      fitok, st);
   }
   HIPCHK(hipStreamWaitEvent(st, ds.ev_seed, 0));
@@ -1163,7 +1248,7 @@ int nls_record_device(int dev, const XT* x, int64_t nrec, int64_t rec_stride, in
     return DFMI_OK;
   }
   // the rest, seeded with each record's buffer-0 result (read on device: no host sync)
-  return lm_device(dev, qi, rows ? qs : nseg, ndata, nrec, nbuf, 1, nbuf - 1, nchunk, out, nbuf, out_ld, nullptr, c,
+  return lm_device(qi, rows ? qs : nseg, ndata, nrec, nbuf, 1, nbuf - 1, nchunk, out, nbuf, out_ld, nullptr, c,
                    jtab, out, out_ld, fitok, st, rows);
 }
 
@@ -1219,14 +1304,14 @@ const std::map<std::string, Knob>& knobs() {
   return k;
 }
 // np.mean / np.var of nrec device records on st (moments.hip), numpy-exact.
-int moments_dev(int dev, const double* dx, int64_t nrec, int64_t rs, int64_t n, double* mean, int64_t mean_stride,
+int moments_dev(const double* dx, int64_t nrec, int64_t rs, int64_t n, double* mean, int64_t mean_stride,
                 double* var, int64_t var_stride, hipStream_t st) {
   const int* plan;
   int64_t nl;
-  int rc = pairwise_plan(dev, n, &plan, &nl);
+  int rc = pairwise_plan(n, &plan, &nl);
   if (rc) return rc;
   void* nodes;
-  if ((rc = workspace(dev, "m_nodes", (size_t)nrec * 2 * nl * 8, &nodes))) return rc;
+  if ((rc = workspace("m_nodes", (size_t)nrec * 2 * nl * 8, &nodes))) return rc;
   HIPCHK(dfmi::moments_launch(dx, nrec, rs, n, plan, nl, (double*)nodes, mean, mean_stride, var, var_stride, st));
   return DFMI_OK;
 }
@@ -1296,7 +1381,7 @@ int ekf_seq_launch(const double* dx, int64_t nrec, int64_t rs, int64_t n, const 
 // zero or at the cap ekf_pit_passes; the channels that stopped contracting or hit the cap are
 // re-run by the sequential kernel. wt: ekf_phase_kernel's table (the sequential kernel's).
 // Returns kPitNoMem, with nothing launched, when a workspace cannot be allocated.
-int ekf_pit_run(int dev, const double* dx, int64_t nrec, int64_t rs, int64_t n, const double* dx0, const double* dp0,
+int ekf_pit_run(const double* dx, int64_t nrec, int64_t rs, int64_t n, const double* dx0, const double* dp0,
                 const double* dq, const double* dr, const double* wt, double w_m, double f_samp, int32_t R,
                 int64_t nbuf, double* dstates, hipStream_t st) {
   // samples per block: the measured best keeps ~16k x nrec^(1/3) blocks in flight over all
@@ -1323,7 +1408,7 @@ int ekf_pit_run(int dev, const double* dx, int64_t nrec, int64_t rs, int64_t n, 
   {
     int rc = 0;
     auto ws = [&](const char* name, size_t bytes, void** p) {
-      if (!rc) rc = workspace(dev, name, bytes, p);
+      if (!rc) rc = workspace(name, bytes, p);
     };
     ws("p_xt", (size_t)(nrec * slots) * 8, &xt);
     ws("p_wt", (size_t)slots * 8, &wtt);
@@ -1398,6 +1483,8 @@ int ekf_pit_run(int dev, const double* dx, int64_t nrec, int64_t rs, int64_t n, 
       hipLaunchKernelGGL(dfmi::ekf_pit_scan_kernel<dfmi::kPitWg>,
                          dim3((unsigned)((lsz[l] + dfmi::kPitWg - 1) / dfmi::kPitWg), nr), dim3(4 * dfmi::kPitWg), 0,
                          st, a[l], lsz[l], lsz[l], l < L ? a[l + 1] : nullptr, (const dfmi::PitChan*)ch);
+    // the fix-ups skip a level's first workgroup (kPitWg elements) and run 64 threads per block
+    static_assert(dfmi::kPitWg == 64, "the fix-up grid (lsz - kPitWg + 63) / 64 assumes 64-element scan workgroups");
     for (int l = L - 1; l >= 1; --l)
       if (lsz[l] > dfmi::kPitWg)
         hipLaunchKernelGGL(topfix && l == L - 1 ? dfmi::ekf_pit_fixup_top_kernel : dfmi::ekf_pit_fixup_kernel,
@@ -1567,36 +1654,26 @@ int ekf_impl(const double* x, int64_t nrec, int64_t rec_stride, int64_t n_samp, 
   g_pit_passes.clear();  // this call's outcome replaces the last one's, whatever path it takes
   g_pit_hist.clear();
   g_pit_hist_n = 0;
-  int dev;
-  int rc = ensure_init(&dev);
+  int rc = ensure_init();
   if (rc) return rc;
   if (nrec == 0) return DFMI_OK;
   hipStream_t st = (hipStream_t)stream;
   const int64_t rs = nrec > 1 ? rec_stride : n_samp;
-  const double *dx = x, *dx0 = x0, *dp0 = p0_diag, *dq = q_diag, *dr = r_val;
-  double* dstates = states;
+  const double *dx, *dx0, *dp0, *dq, *dr;
+  double* dstates;
   const size_t sb = (size_t)nrec * nbuf * 5 * 8;
-  const bool host = mem != DFMI_MEM_DEVICE;
-  if (host) {
-    void *a, *c2, *d, *f;
-    const size_t xb = (size_t)((nrec - 1) * rs + n_samp) * 8;
-    if ((rc = workspace(dev, "e_x", xb > 0 ? xb : 8, &a))) return rc;
-    if ((rc = workspace(dev, "e_p0", 5 * 8, &c2))) return rc;
-    if ((rc = workspace(dev, "e_q", 5 * 8, &d))) return rc;
-    if ((rc = workspace(dev, "e_st", sb > 0 ? sb : 8, &f))) return rc;
-    if (xb) HIPCHK(hipMemcpyAsync(a, x, xb, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(c2, p0_diag, 5 * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d, q_diag, 5 * 8, hipMemcpyHostToDevice, st));
-    dx = (const double*)a;
-    dp0 = (const double*)c2;
-    dq = (const double*)d;
-    dstates = (double*)f;
-  }
+  Staging sg(mem, st);
+  const bool host = sg.host;
+  if ((rc = sg.in("e_x", x, (size_t)((nrec - 1) * rs + n_samp) * 8, &dx))) return rc;
+  if ((rc = sg.in("e_p0", p0_diag, 5 * 8, &dp0))) return rc;
+  if ((rc = sg.in("e_q", q_diag, 5 * 8, &dq))) return rc;
+  if ((rc = sg.out("e_st", states, sb, &dstates))) return rc;
   if (init4) {
-    // x0 = [init4, mean] and r_val (given or np.var) formed on the device
+    // x0 = [init4, mean] and r_val (given or np.var) formed on the device: staged by hand, the
+    // rows come from a kernel (which reads init4 / r_val from the host through its arguments)
     void *b, *e;
-    if ((rc = workspace(dev, "e_x0", (size_t)nrec * 5 * 8, &b))) return rc;
-    if ((rc = workspace(dev, "e_r", (size_t)nrec * 8, &e))) return rc;
+    if ((rc = workspace("e_x0", (size_t)nrec * 5 * 8, &b))) return rc;
+    if ((rc = workspace("e_r", (size_t)nrec * 8, &e))) return rc;
     // init4 in every row (from the device copy when it lives there: no host round trip),
     // then the moments kernels fill x0[r*5+4] and r (an empty record keeps numpy's NaN
     // mean / variance)
@@ -1609,23 +1686,18 @@ int ekf_impl(const double* x, int64_t nrec, int64_t rec_stride, int64_t n_samp, 
                        nrec, host ? (const double*)nullptr : init4, host ? (const double*)nullptr : r_val,
                        r_val != nullptr, hv);
     if (n_samp >= 1) {
-      if ((rc = moments_dev(dev, dx, nrec, rs, n_samp, (double*)b + 4, 5, r_val ? nullptr : (double*)e, 1, st)))
+      if ((rc = moments_dev(dx, nrec, rs, n_samp, (double*)b + 4, 5, r_val ? nullptr : (double*)e, 1, st)))
         return rc;
     }
     dx0 = (const double*)b;
     dr = (const double*)e;
-  } else if (host) {
-    void *b, *e;
-    if ((rc = workspace(dev, "e_x0", (size_t)nrec * 5 * 8, &b))) return rc;
-    if ((rc = workspace(dev, "e_r", (size_t)nrec * 8, &e))) return rc;
-    HIPCHK(hipMemcpyAsync(b, x0, (size_t)nrec * 5 * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(e, r_val, (size_t)nrec * 8, hipMemcpyHostToDevice, st));
-    dx0 = (const double*)b;
-    dr = (const double*)e;
+  } else {
+    if ((rc = sg.in("e_x0", x0, (size_t)nrec * 5 * 8, &dx0))) return rc;
+    if ((rc = sg.in("e_r", r_val, (size_t)nrec * 8, &dr))) return rc;
   }
   if (sb) HIPCHK(hipMemsetAsync(dstates, 0, sb, st));
   void* wtw = nullptr;
-  if ((rc = workspace(dev, "e_wt", (size_t)(n_samp > 0 ? n_samp : 1) * 8, &wtw))) return rc;
+  if ((rc = workspace("e_wt", (size_t)(n_samp > 0 ? n_samp : 1) * 8, &wtw))) return rc;
   if (n_samp > 0)
     hipLaunchKernelGGL(dfmi::ekf_phase_kernel, dim3((unsigned)((n_samp + 255) / 256)), dim3(256), 0, st,
                        (double*)wtw, n_samp, w_m, f_samp);
@@ -1634,7 +1706,7 @@ int ekf_impl(const double* x, int64_t nrec, int64_t rec_stride, int64_t n_samp, 
   // ~37 MB for 400k samples) cannot be allocated do the sequential kernels run instead
   bool pit = t_tune.ekf_pit > 0 && nrec <= t_tune.ekf_pit && n_samp >= t_tune.ekf_pit_min && n_samp >= 2;
   if (pit) {
-    rc = ekf_pit_run(dev, dx, nrec, rs, n_samp, dx0, dp0, dq, dr, (const double*)wtw, w_m, f_samp, R, nbuf, dstates,
+    rc = ekf_pit_run(dx, nrec, rs, n_samp, dx0, dp0, dq, dr, (const double*)wtw, w_m, f_samp, R, nbuf, dstates,
                      st);
     if (rc == kPitNoMem) pit = false;
     else if (rc) return rc;
@@ -1645,11 +1717,7 @@ int ekf_impl(const double* x, int64_t nrec, int64_t rec_stride, int64_t n_samp, 
       return rc;
     g_last_demod = kname;  // also reports the EKF variant
   }
-  if (host) {
-    if (sb) HIPCHK(hipMemcpyAsync(states, dstates, sb, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-  }
-  return DFMI_OK;
+  return sg.finish();
 }
 
 }  // namespace
@@ -1663,24 +1731,18 @@ int demod_impl(const XT* x, int64_t nseg, int64_t seg_stride, int32_t R, int32_t
   CallScope cs(stream);
   if (nseg < 0 || R <= 0 || ndata <= 0 || seg_stride < R) return fail(DFMI_ERR_ARG, "bad demod geometry");
   if (nseg > 0 && (!x || !qi || !dc)) return fail(DFMI_ERR_ARG, "null pointer");
-  int dev;
-  int rc = ensure_init(&dev);
+  int rc = ensure_init();
   if (rc) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  if (mem == DFMI_MEM_DEVICE) return demod_device(dev, x, nseg, seg_stride, R, ndata, w0, period, qi, nseg, dc, st);
   if (nseg == 0) return DFMI_OK;
-  const size_t xb = (size_t)((nseg - 1) * seg_stride + R) * sizeof(XT);
-  void *dx, *dq, *dd;
-  if ((rc = workspace(dev, "h_x", xb, &dx))) return rc;
-  if ((rc = workspace(dev, "h_qi", (size_t)2 * ndata * nseg * 8, &dq))) return rc;
-  if ((rc = workspace(dev, "h_dc", (size_t)nseg * 8, &dd))) return rc;
-  HIPCHK(hipMemcpyAsync(dx, x, xb, hipMemcpyHostToDevice, st));
-  rc = demod_device(dev, (const XT*)dx, nseg, seg_stride, R, ndata, w0, period, (double*)dq, nseg, (double*)dd, st);
-  if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(qi, dq, (size_t)2 * ndata * nseg * 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(dc, dd, (size_t)nseg * 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return DFMI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  Staging sg(mem, st);
+  const XT* dx;
+  double *dq, *dd;
+  if ((rc = sg.in("d_x", x, (size_t)((nseg - 1) * seg_stride + R) * sizeof(XT), &dx))) return rc;
+  if ((rc = sg.out("d_qi", qi, (size_t)2 * ndata * nseg * 8, &dq))) return rc;
+  if ((rc = sg.out("d_dc", dc, (size_t)nseg * 8, &dd))) return rc;
+  if ((rc = demod_device(dx, nseg, seg_stride, R, ndata, w0, period, dq, nseg, dd, st))) return rc;
+  return sg.finish();
 }
 
 template <typename XT>
@@ -1689,25 +1751,25 @@ int demod_rows_impl(const XT* x, int64_t nseg, int64_t seg_stride, int32_t R, in
   CallScope cs(stream);
   if (nseg < 0 || R <= 0 || ndata <= 0 || seg_stride < R) return fail(DFMI_ERR_ARG, "bad demod geometry");
   if (nseg > 0 && (!x || !rows)) return fail(DFMI_ERR_ARG, "null pointer");
-  int dev;
-  int rc = ensure_init(&dev);
+  int rc = ensure_init();
   if (rc) return rc;
   if (nseg == 0) return DFMI_OK;
   hipStream_t st = (hipStream_t)stream;
   const int64_t qs = dfmi_row_stride((int)ndata);
   if (mem == DFMI_MEM_DEVICE) {
-    if (!rows_supported(dev, x, seg_stride, R, ndata, w0, period))
+    if (!rows_supported(x, seg_stride, R, ndata, w0, period))
       return fail(DFMI_ERR_UNSUPPORTED, "row layout needs 16-B rows and an even basis period 128 <= L <= 1024");
-    return demod_device(dev, x, nseg, seg_stride, R, ndata, w0, period, rows, qs, nullptr, st, true);
+    return demod_device(x, nseg, seg_stride, R, ndata, w0, period, rows, qs, nullptr, st, true);
   }
   const size_t xb = (size_t)((nseg - 1) * seg_stride + R) * sizeof(XT);
+  // staged by hand: the support check needs the staged rows' address before anything is uploaded
   void *dx, *dq;
-  if ((rc = workspace(dev, "h_x", xb, &dx))) return rc;
-  if ((rc = workspace(dev, "h_rows", (size_t)qs * nseg * 8, &dq))) return rc;
-  if (!rows_supported(dev, (const XT*)dx, seg_stride, R, ndata, w0, period))
+  if ((rc = workspace("r_x", xb, &dx))) return rc;
+  if ((rc = workspace("r_rows", (size_t)qs * nseg * 8, &dq))) return rc;
+  if (!rows_supported((const XT*)dx, seg_stride, R, ndata, w0, period))
     return fail(DFMI_ERR_UNSUPPORTED, "row layout needs 16-B rows and an even basis period 128 <= L <= 1024");
   HIPCHK(hipMemcpyAsync(dx, x, xb, hipMemcpyHostToDevice, st));
-  rc = demod_device(dev, (const XT*)dx, nseg, seg_stride, R, ndata, w0, period, (double*)dq, qs, nullptr, st, true);
+  rc = demod_device((const XT*)dx, nseg, seg_stride, R, ndata, w0, period, (double*)dq, qs, nullptr, st, true);
   if (rc) return rc;
   HIPCHK(hipMemcpyAsync(rows, dq, (size_t)qs * nseg * 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
@@ -1730,28 +1792,24 @@ int nls_record_impl(const XT* x, int64_t nrec, int64_t rec_stride, int64_t nbuf,
   dfmi::LMConst c;
   int rc = to_lmconst(cfg, &c);
   if (rc) return rc;
-  int dev;
-  if ((rc = ensure_init(&dev))) return rc;
+  if ((rc = ensure_init())) return rc;
   const int64_t nseg = nrec * nbuf;
   if (nseg == 0) return DFMI_OK;
   hipStream_t st = (hipStream_t)stream;
-  if (mem == DFMI_MEM_DEVICE)
-    return nls_record_device(dev, x, nrec, rec_stride, nbuf, R, ndata, w0, period, init_guess, parallel, nchunk, *cfg,
-                             c, out, fitok, st);
+  Staging sg(mem, st);
+  // a staged copy holds the records at the stride the copy's length is computed from (one
+  // record: its own length); device records keep the caller's stride
   const int64_t rs = (nrec > 1) ? rec_stride : nbuf * (int64_t)R;
-  const size_t xb = (size_t)((nrec - 1) * rs + nbuf * (int64_t)R) * sizeof(XT);
-  void *dx, *dout, *dst;
-  if ((rc = workspace(dev, "h_x", xb, &dx))) return rc;
-  if ((rc = workspace(dev, "h_out", (size_t)6 * nseg * 8, &dout))) return rc;
-  if ((rc = workspace(dev, "h_status", (size_t)nseg * 4, &dst))) return rc;
-  HIPCHK(hipMemcpyAsync(dx, x, xb, hipMemcpyHostToDevice, st));
-  rc = nls_record_device(dev, (const XT*)dx, nrec, rs, nbuf, R, ndata, w0, period, init_guess, parallel, nchunk,
-                         *cfg, c, (double*)dout, (int32_t*)dst, st);
-  if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(out, dout, (size_t)6 * nseg * 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(fitok, dst, (size_t)nseg * 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return DFMI_OK;
+  const XT* dx;
+  double* dout;
+  int32_t* dst;
+  if ((rc = sg.in("n_x", x, (size_t)((nrec - 1) * rs + nbuf * (int64_t)R) * sizeof(XT), &dx))) return rc;
+  if ((rc = sg.out("n_out", out, (size_t)6 * nseg * 8, &dout))) return rc;
+  if ((rc = sg.out("n_status", fitok, (size_t)nseg * 4, &dst))) return rc;
+  if ((rc = nls_record_device(dx, nrec, sg.host ? rs : rec_stride, nbuf, R, ndata, w0, period, init_guess, parallel,
+                              nchunk, *cfg, c, dout, dst, st)))
+    return rc;
+  return sg.finish();
 }
 
 
@@ -1784,8 +1842,7 @@ int32_t dfmi_detect_period(double w0, int32_t R, int32_t ndata) { return detect_
 
 int dfmi_device_count(void) {
   CallScope cs;
-  int dev;
-  int rc = ensure_init(&dev);
+  int rc = ensure_init();
   if (rc) return 0;
   return g_ndev;
 }
@@ -1798,8 +1855,7 @@ const char* dfmi_last_demod_kernel(void) { return g_last_demod.c_str(); }
 
 int dfmi_probe_read(int64_t* out, int32_t n) {
   CallScope cs;
-  int dev;
-  if (int rc = ensure_init(&dev)) return rc;
+  if (int rc = ensure_init()) return rc;
   if (!t_ds->probe) return fail(DFMI_ERR_ARG, "probe not enabled on this device (dfmi_set_tuning(\"probe\", 1))");
   if (n < 0 || n > 16 + 2 * dfmi::kProbeWaves || (n && !out)) return fail(DFMI_ERR_ARG, "bad probe read");
   HIPCHK(hipDeviceSynchronize());
@@ -1812,8 +1868,7 @@ int dfmi_get_tuning(const char* key, int64_t* value) {
   if (!key || !value) return fail(DFMI_ERR_ARG, "null argument");
   const std::string k(key);
   if (k == "probe") {
-    int dev;
-    if (int rc = ensure_init(&dev)) return rc;
+    if (int rc = ensure_init()) return rc;
     *value = t_ds->probe ? 1 : 0;
     return DFMI_OK;
   }
@@ -1828,8 +1883,7 @@ int dfmi_set_tuning(const char* key, int64_t value) {
   if (!key) return fail(DFMI_ERR_ARG, "null key");
   const std::string k(key);
   if (k == "probe") {  // per device: a timestamp buffer in this device's memory
-    int dev;
-    if (int rc = ensure_init(&dev)) return rc;
+    if (int rc = ensure_init()) return rc;
     if (value && !t_ds->probe) {
       void* p = nullptr;
       const size_t pb = (16 + 2 * (size_t)dfmi::kProbeWaves) * sizeof(uint64_t);
@@ -1859,8 +1913,7 @@ int dfmi_set_tuning(const char* key, int64_t value) {
 
 int dfmi_step_timing(int32_t enable) {
   CallScope cs;
-  int dev;
-  if (int rc = ensure_init(&dev)) return rc;
+  if (int rc = ensure_init()) return rc;
   t_ds->timing = enable != 0;
   return DFMI_OK;
 }
@@ -1868,8 +1921,7 @@ int dfmi_step_timing(int32_t enable) {
 int dfmi_step_timing_read(double* demod_ms, double* lm_ms, int64_t* nsteps) {
   CallScope cs;
   if (!demod_ms || !lm_ms || !nsteps) return fail(DFMI_ERR_ARG, "null pointer");
-  int dev;
-  if (int rc = ensure_init(&dev)) return rc;
+  if (int rc = ensure_init()) return rc;
   DeviceState& ds = *t_ds;
   double d = 0.0, l = 0.0;
   hipError_t err = hipSuccess;
@@ -1894,8 +1946,7 @@ int dfmi_step_timing_read(double* demod_ms, double* lm_ms, int64_t* nsteps) {
 // call re-allocates what it needs.
 int dfmi_release_workspaces(void) {
   CallScope cs;
-  int dev;
-  if (int rc = ensure_init(&dev)) return rc;
+  if (int rc = ensure_init()) return rc;
   HIPCHK(hipDeviceSynchronize());
   for (auto& kv : t_ds->ws)
     if (int rc = free_stream_ws(kv.second)) return rc;
@@ -1967,42 +2018,32 @@ int dfmi_lm(const double* qi, int64_t nseg, int32_t ndata, const double* guess, 
   dfmi::LMConst c;
   int rc = to_lmconst(cfg, &c);
   if (rc) return rc;
-  int dev;
-  if ((rc = ensure_init(&dev))) return rc;
+  if ((rc = ensure_init())) return rc;
   if (nseg == 0) return DFMI_OK;
   hipStream_t st = (hipStream_t)stream;
   const double* jtab = nullptr;
-  if ((rc = grid_table(dev, ndata, *cfg, &jtab))) return rc;
-  // the kernel writes 6 columns (col 4 = dc is untouched); stage through a workspace
-  void *dq = nullptr, *dg = nullptr, *dout = nullptr, *dst = nullptr;
-  const size_t qib = (size_t)2 * ndata * nseg * 8;
-  const size_t gb = (size_t)(guess_per_segment ? nseg : 1) * 4 * 8;
-  if ((rc = workspace(dev, "lm_out", (size_t)6 * nseg * 8, &dout))) return rc;
-  if ((rc = workspace(dev, "lm_status", (size_t)nseg * 4, &dst))) return rc;
-  if (mem == DFMI_MEM_DEVICE) {
-    dq = (void*)qi;
-    dg = (void*)guess;
-  } else {
-    if ((rc = workspace(dev, "h_qi", qib, &dq))) return rc;
-    if ((rc = workspace(dev, "h_guess", gb, &dg))) return rc;
-    HIPCHK(hipMemcpyAsync(dq, qi, qib, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(dg, guess, gb, hipMemcpyHostToDevice, st));
-  }
+  if ((rc = grid_table(ndata, *cfg, &jtab))) return rc;
+  // the kernel writes 6 columns (col 4 = dc is untouched); stage through a workspace. The results
+  // are staged by hand: they leave that workspace by a copy in device mode too (device to device)
+  Staging sg(mem, st);
+  void *dout = nullptr, *dst = nullptr;
+  const double *dq, *dg;
+  if ((rc = workspace("lm_out", (size_t)6 * nseg * 8, &dout))) return rc;
+  if ((rc = workspace("lm_status", (size_t)nseg * 4, &dst))) return rc;
+  if ((rc = sg.in("lm_qi", qi, (size_t)2 * ndata * nseg * 8, &dq))) return rc;
+  if ((rc = sg.in("lm_guess", guess, (size_t)(guess_per_segment ? nseg : 1) * 4 * 8, &dg))) return rc;
   double* o = (double*)dout;
   if (guess_per_segment) {
-    rc = lm_device(dev, (const double*)dq, nseg, ndata, nseg, 1, 0, 1, 1, (const double*)dg, 4, 1, nullptr, c, jtab, o,
-                   nseg, (int32_t*)dst, st);
+    rc = lm_device(dq, nseg, ndata, nseg, 1, 0, 1, 1, dg, 4, 1, nullptr, c, jtab, o, nseg, (int32_t*)dst, st);
   } else {
-    rc = lm_device(dev, (const double*)dq, nseg, ndata, 1, nseg, 0, nseg, nchunk, (const double*)dg, 4, 1, nullptr,
-                   c, jtab, o, nseg, (int32_t*)dst, st);
+    rc = lm_device(dq, nseg, ndata, 1, nseg, 0, nseg, nchunk, dg, 4, 1, nullptr, c, jtab, o, nseg, (int32_t*)dst, st);
   }
   if (rc) return rc;
-  const hipMemcpyKind kind = (mem == DFMI_MEM_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  const hipMemcpyKind kind = sg.host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
   HIPCHK(hipMemcpyAsync(params, o, (size_t)4 * nseg * 8, kind, st));
   HIPCHK(hipMemcpyAsync(ssq, o + 5 * nseg, (size_t)nseg * 8, kind, st));
   HIPCHK(hipMemcpyAsync(status, dst, (size_t)nseg * 4, kind, st));
-  if (mem != DFMI_MEM_DEVICE) HIPCHK(hipStreamSynchronize(st));
-  return DFMI_OK;
+  return sg.finish();
 }
 
 int dfmi_wdfmi_fit(const double* x, int64_t nrec, int64_t rec_stride, int64_t nbuf, int32_t R,
@@ -2021,8 +2062,7 @@ int dfmi_wdfmi_fit(const double* x, int64_t nrec, int64_t rec_stride, int64_t nb
   if (cfg->method == DFMI_WDFMI_SEQ && (cfg->ndata_psi < 1 || cfg->ndata_psi > 64))
     return fail(DFMI_ERR_UNSUPPORTED, "W-DFMI SEQ: 1 <= ndata_psi <= 64");
   if (nrec * nbuf > 0 && (!x || !witness || !out || !fitok)) return fail(DFMI_ERR_ARG, "null pointer");
-  int dev;
-  int rc = ensure_init(&dev);
+  int rc = ensure_init();
   if (rc) return rc;
   const int64_t nseg = nrec * nbuf;
   if (nseg == 0) return DFMI_OK;
@@ -2051,13 +2091,13 @@ int dfmi_wdfmi_fit(const double* x, int64_t nrec, int64_t rec_stride, int64_t nb
   a.L = 0;
   if (nh > 0 && cfg->period >= 0) a.L = cfg->period > 0 ? cfg->period : detect_period_impl(a.w0, R, nh);
   if (a.L > R) a.L = 0;
-  if ((rc = pairwise_plan(dev, R, &a.pw_plan, nullptr))) return rc;
+  if ((rc = pairwise_plan(R, &a.pw_plan, nullptr))) return rc;
   const size_t lds = dfmi::wdfmi_lds_bytes(a);
   if (lds > t_ds->lds_per_block)
     return fail(DFMI_ERR_UNSUPPORTED, "W-DFMI: R too large for the LDS budget (" + std::to_string(lds) + " B)");
   if (nh > 0 && a.L > 0) {
     const double* bt;
-    if ((rc = basis_table(dev, a.L, nh, a.w0, st, &bt))) return rc;
+    if ((rc = basis_table(a.L, nh, a.w0, &bt))) return rc;
     if (cfg->method == DFMI_WDFMI_NLS) a.btab_nls = bt;
     else a.btab_psi = bt;
   }
@@ -2065,36 +2105,17 @@ int dfmi_wdfmi_fit(const double* x, int64_t nrec, int64_t rec_stride, int64_t nb
   const int64_t ws = nrec > 1 ? wit_stride : 0;
   const int64_t ntmpl = ws == 0 ? 1 : nrec;
   void* tm;
-  if ((rc = workspace(dev, "w_tmpl", (size_t)ntmpl * R * 8, &tm))) return rc;
+  if ((rc = workspace("w_tmpl", (size_t)ntmpl * R * 8, &tm))) return rc;
   a.tmpl = (double*)tm;
   a.rec_stride = rs;
   a.wit_stride = ws;
-  a.x = x;
-  a.wit = witness;
-  a.out = out;
-  a.fitok = fitok;
-  if (mem != DFMI_MEM_DEVICE) {
-    void *dx, *dw, *dout, *dok;
-    const size_t xb = (size_t)((nrec - 1) * rs + nbuf * (int64_t)R) * 8;
-    const size_t wb = (size_t)((ntmpl - 1) * ws + R) * 8;
-    if ((rc = workspace(dev, "w_x", xb, &dx))) return rc;
-    if ((rc = workspace(dev, "w_wit", wb, &dw))) return rc;
-    if ((rc = workspace(dev, "w_out", (size_t)7 * nseg * 8, &dout))) return rc;
-    if ((rc = workspace(dev, "w_ok", (size_t)nseg * 4, &dok))) return rc;
-    HIPCHK(hipMemcpyAsync(dx, x, xb, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(dw, witness, wb, hipMemcpyHostToDevice, st));
-    a.x = (const double*)dx;
-    a.wit = (const double*)dw;
-    a.out = (double*)dout;
-    a.fitok = (int32_t*)dok;
-  }
+  Staging sg(mem, st);
+  if ((rc = sg.in("w_x", x, (size_t)((nrec - 1) * rs + nbuf * (int64_t)R) * 8, &a.x))) return rc;
+  if ((rc = sg.in("w_wit", witness, (size_t)((ntmpl - 1) * ws + R) * 8, &a.wit))) return rc;
+  if ((rc = sg.out("w_out", out, (size_t)7 * nseg * 8, &a.out))) return rc;
+  if ((rc = sg.out("w_ok", fitok, (size_t)nseg * 4, &a.fitok))) return rc;
   HIPCHK(dfmi::wdfmi_launch(a, st));
-  if (mem != DFMI_MEM_DEVICE) {
-    HIPCHK(hipMemcpyAsync(out, a.out, (size_t)7 * nseg * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(fitok, a.fitok, (size_t)nseg * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-  }
-  return DFMI_OK;
+  return sg.finish();
 }
 
 int dfmi_ekf(const double* x, int64_t nrec, int64_t rec_stride, int64_t n_samp, const double* x0,
@@ -2142,23 +2163,20 @@ int dfmi_synth_asd(const dfmi_synth_trial* trials, int64_t ntrial, int64_t n_sam
   CallScope cs(stream);
   if (ntrial < 0 || n_samp < 2 || !(f_samp > 0.0)) return fail(DFMI_ERR_ARG, "bad synthesis geometry (n_samp >= 2)");
   if (ntrial > 0 && (!trials || !out)) return fail(DFMI_ERR_ARG, "null pointer");
-  int dev;
-  int rc = ensure_init(&dev);
+  int rc = ensure_init();
   if (rc) return rc;
   if (ntrial == 0) return DFMI_OK;
   hipStream_t st = (hipStream_t)stream;
-  void *dt, *scr, *dout = out;
-  const size_t ob = (size_t)ntrial * n_samp * 8;
-  if ((rc = workspace(dev, "s_trials", (size_t)ntrial * sizeof(dfmi_synth_trial), &dt))) return rc;
-  if ((rc = workspace(dev, "s_scratch", dfmi::synth_scratch_bytes(ntrial, n_samp), &scr))) return rc;
-  if (mem != DFMI_MEM_DEVICE && (rc = workspace(dev, "s_out", ob, &dout))) return rc;
-  HIPCHK(hipMemcpyAsync(dt, trials, (size_t)ntrial * sizeof(dfmi_synth_trial), hipMemcpyHostToDevice, st));
-  HIPCHK(dfmi::synth_launch((const dfmi_synth_trial*)dt, nullptr, nullptr, ntrial, n_samp, f_samp, scr, (double*)dout,
-                            st));
-  if (mem != DFMI_MEM_DEVICE) HIPCHK(hipMemcpyAsync(out, dout, ob, hipMemcpyDeviceToHost, st));
-  // the trial table is a caller (host) array: done with it only once the copy ran
-  HIPCHK(hipStreamSynchronize(st));
-  return DFMI_OK;
+  Staging sg(mem, st);
+  const dfmi_synth_trial* dt;
+  void* scr;
+  double* dout;
+  // the trial table is a caller (host) array: done with it only once the copy ran (upload)
+  if ((rc = sg.upload("s_trials", trials, (size_t)ntrial * sizeof(dfmi_synth_trial), &dt))) return rc;
+  if ((rc = workspace("s_scratch", dfmi::synth_scratch_bytes(ntrial, n_samp), &scr))) return rc;
+  if ((rc = sg.out("s_out", out, (size_t)ntrial * n_samp * 8, &dout))) return rc;
+  HIPCHK(dfmi::synth_launch(dt, nullptr, nullptr, ntrial, n_samp, f_samp, scr, dout, st));
+  return sg.finish();
 }
 
 // the argument checks dfmi_plnoise and dfmi_synth_asd_coloured share (host side, before any device work)
@@ -2179,23 +2197,19 @@ int dfmi_plnoise(const double* sections, int32_t nsec, double scale, double sigm
   if (rc) return rc;
   if (nser < 0 || nser > INT32_MAX || !std::isfinite(sigma)) return fail(DFMI_ERR_ARG, "plnoise: 0 <= nser < 2^31, sigma finite");
   if (nser > 0 && (!seeds || !out)) return fail(DFMI_ERR_ARG, "null pointer");
-  int dev;
-  if ((rc = ensure_init(&dev))) return rc;
+  if ((rc = ensure_init())) return rc;
   if (nser == 0) return DFMI_OK;
   hipStream_t st = (hipStream_t)stream;
-  void *dsec, *dseed, *dout = out;
-  const size_t ob = (size_t)nser * n * 8;
-  if ((rc = workspace(dev, "p_sections", (size_t)3 * nsec * 8, &dsec))) return rc;
-  if ((rc = workspace(dev, "p_seeds", (size_t)nser * 4, &dseed))) return rc;
-  if (mem != DFMI_MEM_DEVICE && (rc = workspace(dev, "p_out", ob, &dout))) return rc;
-  HIPCHK(hipMemcpyAsync(dsec, sections, (size_t)3 * nsec * 8, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(dseed, seeds, (size_t)nser * 4, hipMemcpyHostToDevice, st));
-  HIPCHK(dfmi::plnoise_launch((const double*)dsec, nsec, scale, (const uint32_t*)dseed, sigma, nullptr, nser, n_warm, n,
-                              (double*)dout, st));
-  if (mem != DFMI_MEM_DEVICE) HIPCHK(hipMemcpyAsync(out, dout, ob, hipMemcpyDeviceToHost, st));
-  // sections and seeds are caller (host) arrays: done with them only once the copies ran
-  HIPCHK(hipStreamSynchronize(st));
-  return DFMI_OK;
+  Staging sg(mem, st);
+  const double* dsec;
+  const uint32_t* dseed;
+  double* dout;
+  // sections and seeds are caller (host) arrays: done with them only once the copies ran (upload)
+  if ((rc = sg.upload("pl_sections", sections, (size_t)3 * nsec * 8, &dsec))) return rc;
+  if ((rc = sg.upload("pl_seeds", seeds, (size_t)nser * 4, &dseed))) return rc;
+  if ((rc = sg.out("pl_out", out, (size_t)nser * n * 8, &dout))) return rc;
+  HIPCHK(dfmi::plnoise_launch(dsec, nsec, scale, dseed, sigma, nullptr, nser, n_warm, n, dout, st));
+  return sg.finish();
 }
 
 int dfmi_synth_asd_coloured(const dfmi_synth_trial* trials, const dfmi_synth_colour* colour, const double* sections,
@@ -2214,28 +2228,26 @@ int dfmi_synth_asd_coloured(const dfmi_synth_trial* trials, const dfmi_synth_col
     if (!std::isfinite(colour[r].sigma) || !std::isfinite(colour[r].g_freq) || !std::isfinite(colour[r].g_arm) ||
         !std::isfinite(colour[r].f0))
       return fail(DFMI_ERR_ARG, "synth_asd_coloured: a colour row is not finite");
-  int dev;
-  if ((rc = ensure_init(&dev))) return rc;
+  if ((rc = ensure_init())) return rc;
   hipStream_t st = (hipStream_t)stream;
-  void *dt, *dc, *dsec, *scr, *basis, *dout = out;
+  Staging sg(mem, st);
+  const dfmi_synth_trial* dt;
+  const dfmi_synth_colour* dc;
+  const double* dsec;
+  void *scr, *basis;
+  double* dout;
   const size_t ob = (size_t)ntrial * n_samp * 8;
-  if ((rc = workspace(dev, "s_trials", (size_t)ntrial * sizeof(dfmi_synth_trial), &dt))) return rc;
-  if ((rc = workspace(dev, "s_colour", (size_t)ntrial * sizeof(dfmi_synth_colour), &dc))) return rc;
-  if ((rc = workspace(dev, "p_sections", (size_t)3 * nsec * 8, &dsec))) return rc;
-  if ((rc = workspace(dev, "s_scratch", dfmi::synth_scratch_bytes(ntrial, n_samp), &scr))) return rc;
-  if ((rc = workspace(dev, "s_basis", ob, &basis))) return rc;
-  if (mem != DFMI_MEM_DEVICE && (rc = workspace(dev, "s_out", ob, &dout))) return rc;
-  HIPCHK(hipMemcpyAsync(dt, trials, (size_t)ntrial * sizeof(dfmi_synth_trial), hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(dc, colour, (size_t)ntrial * sizeof(dfmi_synth_colour), hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(dsec, sections, (size_t)3 * nsec * 8, hipMemcpyHostToDevice, st));
+  // trials, colour rows and sections are caller (host) arrays in both modes (upload)
+  if ((rc = sg.upload("c_trials", trials, (size_t)ntrial * sizeof(dfmi_synth_trial), &dt))) return rc;
+  if ((rc = sg.upload("c_colour", colour, (size_t)ntrial * sizeof(dfmi_synth_colour), &dc))) return rc;
+  if ((rc = sg.upload("c_sections", sections, (size_t)3 * nsec * 8, &dsec))) return rc;
+  if ((rc = workspace("c_scratch", dfmi::synth_scratch_bytes(ntrial, n_samp), &scr))) return rc;
+  if ((rc = workspace("c_basis", ob, &basis))) return rc;
+  if ((rc = sg.out("c_out", out, ob, &dout))) return rc;
   // the basis series of every coloured trial, then the trials over them (same stream: in order)
-  HIPCHK(dfmi::plnoise_launch((const double*)dsec, nsec, scale, nullptr, 0.0, (const dfmi_synth_colour*)dc, ntrial,
-                              n_warm, n_samp, (double*)basis, st));
-  HIPCHK(dfmi::synth_launch((const dfmi_synth_trial*)dt, (const dfmi_synth_colour*)dc, (const double*)basis, ntrial,
-                            n_samp, f_samp, scr, (double*)dout, st));
-  if (mem != DFMI_MEM_DEVICE) HIPCHK(hipMemcpyAsync(out, dout, ob, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return DFMI_OK;
+  HIPCHK(dfmi::plnoise_launch(dsec, nsec, scale, nullptr, 0.0, dc, ntrial, n_warm, n_samp, (double*)basis, st));
+  HIPCHK(dfmi::synth_launch(dt, dc, (const double*)basis, ntrial, n_samp, f_samp, scr, dout, st));
+  return sg.finish();
 }
 
 int dfmi_synth_snr(const dfmi_snr_params* prm, int64_t idx0, int64_t n, double* out, int32_t mem, void* stream) {
@@ -2243,19 +2255,15 @@ int dfmi_synth_snr(const dfmi_snr_params* prm, int64_t idx0, int64_t n, double* 
   if (!prm || n < 0 || idx0 < 0) return fail(DFMI_ERR_ARG, "bad snr synthesis arguments");
   if (!(prm->f_samp > 0.0) || prm->period < 0) return fail(DFMI_ERR_ARG, "f_samp must be > 0, period >= 0");
   if (n > 0 && !out) return fail(DFMI_ERR_ARG, "null pointer");
-  int dev;
-  int rc = ensure_init(&dev);
+  int rc = ensure_init();
   if (rc) return rc;
   if (n == 0) return DFMI_OK;
   hipStream_t st = (hipStream_t)stream;
-  double* dout = out;
-  if (mem != DFMI_MEM_DEVICE && (rc = workspace(dev, "g_out", (size_t)n * 8, (void**)&dout))) return rc;
+  Staging sg(mem, st);
+  double* dout;
+  if ((rc = sg.out("g_out", out, (size_t)n * 8, &dout))) return rc;
   HIPCHK(dfmi::snr_gen_launch(*prm, idx0, n, dout, t_ds->n_cu, st));
-  if (mem != DFMI_MEM_DEVICE) {
-    HIPCHK(hipMemcpyAsync(out, dout, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-  }
-  return DFMI_OK;
+  return sg.finish();
 }
 
 int dfmi_bessel_eval(const double* x, int64_t nx, int32_t nmax, int32_t method, double* out, int32_t mem,
@@ -2265,28 +2273,17 @@ int dfmi_bessel_eval(const double* x, int64_t nx, int32_t nmax, int32_t method, 
   if ((method == 1 && nmax > 13) || (method == 2 && nmax > 17))
     return fail(DFMI_ERR_ARG, "register path: nmax <= 13 (method 1) / 17 (method 2)");
   if (nx > 0 && (!x || !out)) return fail(DFMI_ERR_ARG, "null pointer");
-  int dev;
-  int rc = ensure_init(&dev);
+  int rc = ensure_init();
   if (rc) return rc;
   if (nx == 0) return DFMI_OK;
   hipStream_t st = (hipStream_t)stream;
-  const size_t ob = (size_t)nx * (nmax + 1) * 8;
-  const double* dx = x;
-  double* dout = out;
-  if (mem != DFMI_MEM_DEVICE) {
-    void *a, *b;
-    if ((rc = workspace(dev, "b_x", (size_t)nx * 8, &a))) return rc;
-    if ((rc = workspace(dev, "b_out", ob, &b))) return rc;
-    HIPCHK(hipMemcpyAsync(a, x, (size_t)nx * 8, hipMemcpyHostToDevice, st));
-    dx = (const double*)a;
-    dout = (double*)b;
-  }
+  Staging sg(mem, st);
+  const double* dx;
+  double* dout;
+  if ((rc = sg.in("b_x", x, (size_t)nx * 8, &dx))) return rc;
+  if ((rc = sg.out("b_out", out, (size_t)nx * (nmax + 1) * 8, &dout))) return rc;
   HIPCHK(dfmi::bessel_eval_launch(dx, nx, nmax, method, dout, st));
-  if (mem != DFMI_MEM_DEVICE) {
-    HIPCHK(hipMemcpyAsync(out, dout, ob, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-  }
-  return DFMI_OK;
+  return sg.finish();
 }
 
 int dfmi_fisher(const double* params, int64_t n, int64_t ld, int32_t ndata, const double* var, double var_mul,
@@ -2295,8 +2292,7 @@ int dfmi_fisher(const double* params, int64_t n, int64_t ld, int32_t ndata, cons
   if (n < 0 || ld < n || ndata <= 0) return fail(DFMI_ERR_ARG, "bad fisher geometry (n >= 0, ld >= n, ndata > 0)");
   if (!jtj && !cov && !sigma) return fail(DFMI_ERR_ARG, "fisher: one of jtj, cov, sigma is required");
   if (n > 0 && !params) return fail(DFMI_ERR_ARG, "null pointer");
-  int dev;
-  int rc = ensure_init(&dev);
+  int rc = ensure_init();
   if (rc) return rc;
   if (n == 0) return DFMI_OK;
   hipStream_t st = (hipStream_t)stream;
@@ -2305,11 +2301,12 @@ int dfmi_fisher(const double* params, int64_t n, int64_t ld, int32_t ndata, cons
     return DFMI_OK;
   }
   // host memory: the four parameter rows (and var) packed with ld = n, the outputs behind them
+  // (staged by hand: rows repacked at another stride, optional outputs inside one block)
   void *din, *dout, *dok;
   const size_t rb = (size_t)n * 8;
-  if ((rc = workspace(dev, "f_in", 5 * rb, &din))) return rc;
-  if ((rc = workspace(dev, "f_out", 24 * rb, &dout))) return rc;
-  if ((rc = workspace(dev, "f_ok", (size_t)n * 4, &dok))) return rc;
+  if ((rc = workspace("f_in", 5 * rb, &din))) return rc;
+  if ((rc = workspace("f_out", 24 * rb, &dout))) return rc;
+  if ((rc = workspace("f_ok", (size_t)n * 4, &dok))) return rc;
   double* dp = (double*)din;
   for (int i = 0; i < 4; ++i)
     HIPCHK(hipMemcpyAsync(dp + (size_t)i * n, params + (size_t)i * ld, rb, hipMemcpyHostToDevice, st));
@@ -2348,8 +2345,7 @@ int dfmi_lpsd(const double* x, int64_t nser, int64_t ser_stride, int64_t N, doub
   for (int64_t j = 0; j < J; ++j)
     if (L[j] < 1 || L[j] > N || K[j] < 1 || K[j] > INT32_MAX || !(b[j] >= 0.0) || !std::isfinite(b[j]))
       return fail(DFMI_ERR_ARG, "lpsd: a plan entry is outside 1 <= L <= N, K >= 1, b >= 0");
-  int dev;
-  int rc = ensure_init(&dev);
+  int rc = ensure_init();
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
 
@@ -2392,23 +2388,23 @@ int dfmi_lpsd(const double* x, int64_t nser, int64_t ser_stride, int64_t N, doub
     p = bt.p1;
   }
   void *dtab, *dwin, *dtile, *dwsum;
-  if ((rc = workspace(dev, "p_tab", up.size() * 8, &dtab))) return rc;
-  if ((rc = workspace(dev, "p_win", max_w * 8, &dwin))) return rc;
-  if ((rc = workspace(dev, "p_tile", max_t * (size_t)nser * 8, &dtile))) return rc;
-  if ((rc = workspace(dev, "p_wsum", max_f * 16, &dwsum))) return rc;
+  if ((rc = workspace("lp_tab", up.size() * 8, &dtab))) return rc;
+  if ((rc = workspace("lp_win", max_w * 8, &dwin))) return rc;
+  if ((rc = workspace("lp_tile", max_t * (size_t)nser * 8, &dtile))) return rc;
+  if ((rc = workspace("lp_wsum", max_f * 16, &dwsum))) return rc;
+  Staging sg(mem, st);
   const double* dx = x;
-  double *ds = Sxx, *de = enbw;
+  double *ds, *de;
   const int64_t stride = nser > 1 ? ser_stride : N;
-  if (mem != DFMI_MEM_DEVICE) {
-    void *a, *o;
-    if ((rc = workspace(dev, "p_x", (size_t)nser * (size_t)N * 8, &a))) return rc;
-    if ((rc = workspace(dev, "p_out", ((size_t)nser + 1) * (size_t)J * 8, &o))) return rc;
+  if (sg.host) {  // the series staged by hand: one copy each, packed at stride N
+    void* a;
+    if ((rc = workspace("lp_x", (size_t)nser * (size_t)N * 8, &a))) return rc;
     for (int64_t r = 0; r < nser; ++r)
       HIPCHK(hipMemcpyAsync((double*)a + (size_t)r * N, x + (size_t)r * stride, (size_t)N * 8, hipMemcpyHostToDevice, st));
     dx = (const double*)a;
-    ds = (double*)o;
-    de = ds + (size_t)nser * J;
   }
+  if ((rc = sg.out("lp_sxx", Sxx, (size_t)nser * J * 8, &ds))) return rc;
+  if ((rc = sg.out("lp_enbw", enbw, (size_t)J * 8, &de))) return rc;
   // the tables are this call's own host memory: uploaded before the call returns
   HIPCHK(hipMemcpyAsync(dtab, up.data(), up.size() * 8, hipMemcpyHostToDevice, st));
   HIPCHK(hipStreamSynchronize(st));
@@ -2421,16 +2417,11 @@ int dfmi_lpsd(const double* x, int64_t nser, int64_t ser_stride, int64_t N, doub
       ++n256;
       t256 += hf[p].K;
     }
-    HIPCHK(dfmi::lpsd_batch_launch(dx, nser, mem != DFMI_MEM_DEVICE ? N : stride, N, fs, df + bt.p0, (int)(bt.p1 - bt.p0),
+    HIPCHK(dfmi::lpsd_batch_launch(dx, nser, sg.host ? N : stride, N, fs, df + bt.p0, (int)(bt.p1 - bt.p0),
                                    n256, hf[bt.p0].L, t256, bt.nt - t256, order, pa, inv_i0, drk2, hf[bt.p0].woff,
                                    (double*)dwin, (double*)dwsum, hf[bt.p0].toff, bt.nt, (double*)dtile, J, ds, de, st));
   }
-  if (mem != DFMI_MEM_DEVICE) {
-    HIPCHK(hipMemcpyAsync(Sxx, ds, (size_t)nser * J * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(enbw, de, (size_t)J * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-  }
-  return DFMI_OK;
+  return sg.finish();
 }
 
 int dfmi_record_moments(const double* x, int64_t nrec, int64_t rec_stride, int64_t n, double* mean, double* var,
@@ -2439,30 +2430,19 @@ int dfmi_record_moments(const double* x, int64_t nrec, int64_t rec_stride, int64
   if (nrec < 0 || n < 1 || n > INT32_MAX) return fail(DFMI_ERR_ARG, "bad moments geometry (1 <= n < 2^31)");
   if (nrec > 1 && rec_stride < n) return fail(DFMI_ERR_ARG, "rec_stride < n");
   if (nrec > 0 && (!x || !mean)) return fail(DFMI_ERR_ARG, "null pointer");
-  int dev;
-  int rc = ensure_init(&dev);
+  int rc = ensure_init();
   if (rc) return rc;
   if (nrec == 0) return DFMI_OK;
   hipStream_t st = (hipStream_t)stream;
   const int64_t rs = nrec > 1 ? rec_stride : n;
-  const double* dx = x;
-  double *dm = mean, *dv = var;
-  if (mem != DFMI_MEM_DEVICE) {
-    void *a, *b;
-    if ((rc = workspace(dev, "m_x", (size_t)((nrec - 1) * rs + n) * 8, &a))) return rc;
-    if ((rc = workspace(dev, "m_out", (size_t)nrec * 16, &b))) return rc;
-    HIPCHK(hipMemcpyAsync(a, x, (size_t)((nrec - 1) * rs + n) * 8, hipMemcpyHostToDevice, st));
-    dx = (const double*)a;
-    dm = (double*)b;
-    dv = var ? dm + nrec : nullptr;
-  }
-  if ((rc = moments_dev(dev, dx, nrec, rs, n, dm, 1, dv, 1, st))) return rc;
-  if (mem != DFMI_MEM_DEVICE) {
-    HIPCHK(hipMemcpyAsync(mean, dm, (size_t)nrec * 8, hipMemcpyDeviceToHost, st));
-    if (var) HIPCHK(hipMemcpyAsync(var, dv, (size_t)nrec * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-  }
-  return DFMI_OK;
+  Staging sg(mem, st);
+  const double* dx;
+  double *dm, *dv = nullptr;
+  if ((rc = sg.in("m_x", x, (size_t)((nrec - 1) * rs + n) * 8, &dx))) return rc;
+  if ((rc = sg.out("m_mean", mean, (size_t)nrec * 8, &dm))) return rc;
+  if (var && (rc = sg.out("m_var", var, (size_t)nrec * 8, &dv))) return rc;
+  if ((rc = moments_dev(dx, nrec, rs, n, dm, 1, dv, 1, st))) return rc;
+  return sg.finish();
 }
 
 }  // extern "C"
