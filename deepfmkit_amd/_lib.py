@@ -32,7 +32,7 @@ SYMBOLS = ("dfmi_lm_config_default", "dfmi_demod", "dfmi_lm", "dfmi_nls_record",
            "dfmi_release_workspaces", "dfmi_step_timing", "dfmi_step_timing_read", "dfmi_ekf_pit_passes",
            "dfmi_ekf_pit_trace", "dfmi_demod_typed", "dfmi_demod_rows_typed", "dfmi_nls_record_typed",
            "dfmi_fisher", "dfmi_lpsd_plan", "dfmi_lpsd", "dfmi_plnoise_design", "dfmi_plnoise",
-           "dfmi_synth_asd_coloured")
+           "dfmi_synth_asd_coloured", "dfmi_lcsd")
 
 
 class DFMIError(RuntimeError):
@@ -239,6 +239,8 @@ def load():
         lib.dfmi_lpsd_plan.restype = i64
         lib.dfmi_lpsd.argtypes = [P, i64, i64, i64, dbl, P, P, P, i64, i32, dbl, P, P, i32, P]
         lib.dfmi_lpsd.restype = ctypes.c_int
+        lib.dfmi_lcsd.argtypes = [P, i64, P, i64, i64, i64, dbl, P, P, P, i64, i32, dbl, P, P, P, P, P, P, i32, P]
+        lib.dfmi_lcsd.restype = ctypes.c_int
         lib.dfmi_wdfmi_fit.argtypes = [P, i64, i64, i64, i32, P, i64, ctypes.POINTER(WdfmiConfig), P, P, i32, P]
         lib.dfmi_wdfmi_fit.restype = ctypes.c_int
         lib.dfmi_detect_period.argtypes = [dbl, i32, i32]

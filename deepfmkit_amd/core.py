@@ -387,3 +387,34 @@ class DeepFitFramework:
             r = lpsd(np.stack([x for _, x, _ in fits]), fits[0][0].fs, **fits[0][2])
             for i, (fit, _, _) in enumerate(fits):
                 fit.f, fit.Sxx = r.f.copy(), np.ascontiguousarray(r.Sxx[i])
+
+    def calc_lcsd(self, label_x, label_y, which="phi"):
+        """Cross-spectral density, coherence, transfer estimate and residual of the fitted
+        `which` of two fits (deepfmkit_amd.lpsd.lcsd): the LCSDResult of
+        (label_x, label_y), or for a list label_y a dict by label from one GPU call that shares
+        x (one witness against several channels). The fits must agree in length, data rate and
+        LPSD settings (ValueError). A label without a fit logs calc_lpsd's warning and returns
+        None. Nothing is stored on the fits."""
+        from .lpsd import LCSDResult, lcsd
+        many = isinstance(label_y, (list, tuple))
+        got = []
+        for label in [label_x] + (list(label_y) if many else [label_y]):
+            try:
+                fit = self.fits[label]
+                x = np.asarray(getattr(fit, which), dtype=np.float64).reshape(-1)
+                st = fit.lpsd_settings()
+            except (KeyError, TypeError, AttributeError):
+                log.warning("Specified label is invalid!")
+                return None
+            got.append((label, x, float(fit.fs), st))
+        _, x, fs, st = got[0]
+        for label, y, fs_y, st_y in got[1:]:
+            if y.size != x.size or fs_y != fs or st_y != st:
+                raise ValueError(f"calc_lcsd: '{label}' and '{label_x}' differ in length, fs or LPSD settings")
+        if not many:
+            return lcsd(x, got[1][1], fs, **st)
+        if not got[1:]:
+            return {}
+        r = lcsd(x, np.stack([y for _, y, _, _ in got[1:]]), fs, **st)
+        return {label: LCSDResult(r.f, r.Sxx[i], r.Syy[i], r.Sxy[i], r.coh[i], r.H[i], r.resid[i], r.enbw, r.L, r.K, r.b)
+                for i, (label, _, _, _) in enumerate(got[1:])}

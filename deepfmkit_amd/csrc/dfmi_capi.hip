@@ -41,6 +41,12 @@ hipError_t lpsd_batch_launch(const double* x, int64_t nser, int64_t ser_stride, 
                              int order, double pa, double inv_i0, const double* rk2, int64_t woff0, double* win,
                              double* wsum, int64_t toff0, int64_t tiles_ld, double* tile, int64_t J, double* Sxx,
                              double* enbw, hipStream_t st);
+hipError_t lcsd_batch_launch(const double* x, int64_t x_stride, const double* y, int64_t y_stride, int64_t npair,
+                             int64_t N, double fs, const LpsdFreq* fr, int nf, int n256, int64_t maxL, int64_t tiles256,
+                             int64_t tiles64, int order, double pa, double inv_i0, const double* rk2, int64_t woff0,
+                             double* win, double* wsum, int64_t toff0, int64_t tiles_ld, double* tile, int64_t J,
+                             double* Sxx, double* Syy, double* Sxy_re, double* Sxy_im, double* coh, double* enbw,
+                             hipStream_t st);
 hipError_t snr_gen_launch(const dfmi_snr_params& p, int64_t idx0, int64_t n, double* out, int n_cu, hipStream_t st);
 hipError_t bessel_eval_launch(const double* x, int64_t nx, int nmax, int method, double* out, hipStream_t st);
 hipError_t fisher_launch(const double* params, int64_t n, int64_t ld, int ndata, const double* var, double var_mul,
@@ -188,6 +194,7 @@ struct DeviceState {
   std::map<std::tuple<int, int, uint64_t>, DevBuf> basis;            // (L, ndata, w0 bits); (L, -(8 ndata + no), w0 bits): wide
   std::map<std::tuple<int, uint64_t, uint64_t, uint64_t>, DevBuf> gridtab;  // (ndata, min, max, step)
   std::map<int64_t, DevBuf> pwplan;                                 // n -> numpy pairwise-sum plan
+  std::map<int, DevBuf> lpsd_rk2;                                    // 0 -> the 1/k^2 table of lpsd_i0
   std::map<std::pair<const void*, int>, int> occupancy;              // (kernel, LDS bytes) -> blocks per CU
   std::mutex mu;               // held by the call that drives this device (CallScope)
   hipStream_t side = nullptr;  // seed step runs here, concurrently with the bulk demod (unfused layouts)
@@ -2324,10 +2331,113 @@ int dfmi_fisher(const double* params, int64_t n, int64_t ld, int32_t ndata, cons
   return DFMI_OK;
 }
 
-// dfmi_lpsd's window and tile workspaces together stay within lpsd_batch_mb (tuning key,
-// default 512 MiB) per batch of frequencies; a batch always holds at least one frequency
-// (one frequency's window is at most N doubles and its tiles nser x K).
+}  // extern "C"
+
+namespace {
+
+// dfmi_lpsd's and dfmi_lcsd's window and tile workspaces together stay within lpsd_batch_mb
+// (tuning key, default 512 MiB) per batch of frequencies; a batch always holds at least one
+// frequency (one frequency's window is at most N doubles and its tiles per_slot x K).
 constexpr int kLpsdBatchFreqs = 32768;
+
+// What the two calls share, so that it stands once: the argument checks after each call's own
+// geometry check (lpsd_args), then the frequency sort, the tables, the batch split and the
+// workspaces (lpsd_setup).
+int lpsd_args(int64_t N, int64_t J, double fs, int32_t order, double psll, const double* b, const int64_t* L,
+              const int64_t* K, bool pointers, double* pa) {
+  if (!(fs > 0.0) || !std::isfinite(fs)) return fail(DFMI_ERR_ARG, "lpsd: fs must be positive and finite");
+  if (order != 0 && order != -1) return fail(DFMI_ERR_ARG, "lpsd: order must be 0 (segment mean removed) or -1 (nothing)");
+  if (!pointers || !b || !L || !K) return fail(DFMI_ERR_ARG, "null pointer");
+  *pa = dfmi::kLpsdPi * dfmi::lpsd_kaiser_alpha(psll);
+  if (!(*pa > 0.0 && *pa <= dfmi::kLpsdI0Max))
+    return fail(DFMI_ERR_ARG, "lpsd: psll outside the Kaiser fit's range (0 < pi alpha(psll) <= 64)");
+  for (int64_t j = 0; j < J; ++j)
+    if (L[j] < 1 || L[j] > N || K[j] < 1 || K[j] > INT32_MAX || !(b[j] >= 0.0) || !std::isfinite(b[j]))
+      return fail(DFMI_ERR_ARG, "lpsd: a plan entry is outside 1 <= L <= N, K >= 1, b >= 0");
+  return DFMI_OK;
+}
+
+struct LpsdSetup {
+  struct Batch {
+    int64_t p0, p1, nw, nt;  // frequencies [p0, p1) of the sorted table, their window samples and tile slots
+    int n256;                // the first n256 of them have L > kLpsdWaveL
+    int64_t t256;            // and t256 of the nt slots
+  };
+  std::vector<dfmi::LpsdFreq> hf;  // sorted longest segment first (stable)
+  std::vector<Batch> batches;
+  double inv_i0;
+  const dfmi::LpsdFreq* df;  // hf on the device
+  const double* drk2;        // the 1/k^2 table of lpsd_i0 (cached per device)
+  double *dwin, *dtile, *dwsum;
+};
+
+// per_slot: doubles a tile slot takes in the tile workspace (dfmi_lpsd: nser; dfmi_lcsd: 4 npair).
+// The plan is the caller's host memory: its table is uploaded before this returns.
+int lpsd_setup(const double* b, const int64_t* L, const int64_t* K, int64_t J, size_t per_slot, double pa,
+               hipStream_t st, LpsdSetup* s) {
+  std::vector<int64_t> ord((size_t)J);
+  for (int64_t j = 0; j < J; ++j) ord[(size_t)j] = j;
+  std::stable_sort(ord.begin(), ord.end(), [&](int64_t a, int64_t c) { return L[a] > L[c]; });
+  s->hf.resize((size_t)J);
+  int64_t woff = 0, toff = 0;
+  for (int64_t p = 0; p < J; ++p) {  // window rows and tile slots in the sorted order
+    const int64_t j = ord[(size_t)p];
+    s->hf[(size_t)p] = dfmi::LpsdFreq{b[j], L[j], K[j], woff, toff, j};
+    woff += L[j];
+    toff += K[j];
+  }
+  // batches of consecutive frequencies within the workspace bound
+  const size_t kLpsdBatchBytes = (size_t)t_tune.lpsd_batch_mb << 20;
+  const std::vector<dfmi::LpsdFreq>& hf = s->hf;
+  size_t max_w = 0, max_t = 0, max_f = 0;
+  for (int64_t p = 0; p < J;) {
+    LpsdSetup::Batch bt{p, p, 0, 0, 0, 0};
+    while (bt.p1 < J && bt.p1 - bt.p0 < kLpsdBatchFreqs) {
+      const int64_t nw = bt.nw + hf[(size_t)bt.p1].L, nt = bt.nt + hf[(size_t)bt.p1].K;
+      if (bt.p1 > bt.p0 && ((size_t)nw + (size_t)nt * per_slot) * 8 > kLpsdBatchBytes) break;
+      bt.nw = nw;
+      bt.nt = nt;
+      ++bt.p1;
+    }
+    if ((size_t)bt.nt > ((size_t)1 << 30)) return fail(DFMI_ERR_UNSUPPORTED, "lpsd: more than 2^30 segments at one frequency");
+    for (int64_t q = bt.p0; q < bt.p1 && hf[(size_t)q].L > dfmi::kLpsdWaveL; ++q) {
+      ++bt.n256;
+      bt.t256 += hf[(size_t)q].K;
+    }
+    max_w = std::max(max_w, (size_t)bt.nw);
+    max_t = std::max(max_t, (size_t)bt.nt);
+    max_f = std::max(max_f, (size_t)(bt.p1 - bt.p0));
+    s->batches.push_back(bt);
+    p = bt.p1;
+  }
+  double hrk2[dfmi::kLpsdI0Terms];
+  dfmi::lpsd_fill_rk2(hrk2);
+  s->inv_i0 = 1.0 / dfmi::lpsd_i0(pa, hrk2);
+  const DevBuf* rk2;
+  int rc;
+  if ((rc = cached_upload(t_ds->lpsd_rk2, 0, [&](int64_t*) {
+         return std::vector<double>(hrk2, hrk2 + dfmi::kLpsdI0Terms);
+       }, &rk2)))
+    return rc;
+  s->drk2 = (const double*)rk2->p;
+  void *dtab, *dwin, *dtile, *dwsum;
+  const size_t tab_bytes = (size_t)J * sizeof(dfmi::LpsdFreq);
+  if ((rc = workspace("lp_tab", tab_bytes, &dtab))) return rc;
+  if ((rc = workspace("lp_win", max_w * 8, &dwin))) return rc;
+  if ((rc = workspace("lp_tile", max_t * per_slot * 8, &dtile))) return rc;
+  if ((rc = workspace("lp_wsum", max_f * 16, &dwsum))) return rc;
+  HIPCHK(hipMemcpyAsync(dtab, hf.data(), tab_bytes, hipMemcpyHostToDevice, st));
+  HIPCHK(hipStreamSynchronize(st));
+  s->df = (const dfmi::LpsdFreq*)dtab;
+  s->dwin = (double*)dwin;
+  s->dtile = (double*)dtile;
+  s->dwsum = (double*)dwsum;
+  return DFMI_OK;
+}
+
+}  // namespace
+
+extern "C" {
 
 int dfmi_lpsd(const double* x, int64_t nser, int64_t ser_stride, int64_t N, double fs, const double* b,
               const int64_t* L, const int64_t* K, int64_t J, int32_t order, double psll, double* Sxx, double* enbw,
@@ -2336,62 +2446,13 @@ int dfmi_lpsd(const double* x, int64_t nser, int64_t ser_stride, int64_t N, doub
   if (nser < 1 || nser > 65535 || N < 1 || N > INT32_MAX || J < 1 || J > INT32_MAX)
     return fail(DFMI_ERR_ARG, "bad lpsd geometry (1 <= nser <= 65535, 1 <= N < 2^31, J >= 1)");
   if (nser > 1 && ser_stride < N) return fail(DFMI_ERR_ARG, "ser_stride < N");
-  if (!(fs > 0.0) || !std::isfinite(fs)) return fail(DFMI_ERR_ARG, "lpsd: fs must be positive and finite");
-  if (order != 0 && order != -1) return fail(DFMI_ERR_ARG, "lpsd: order must be 0 (segment mean removed) or -1 (nothing)");
-  if (!x || !b || !L || !K || !Sxx || !enbw) return fail(DFMI_ERR_ARG, "null pointer");
-  const double pa = dfmi::kLpsdPi * dfmi::lpsd_kaiser_alpha(psll);
-  if (!(pa > 0.0 && pa <= dfmi::kLpsdI0Max))
-    return fail(DFMI_ERR_ARG, "lpsd: psll outside the Kaiser fit's range (0 < pi alpha(psll) <= 64)");
-  for (int64_t j = 0; j < J; ++j)
-    if (L[j] < 1 || L[j] > N || K[j] < 1 || K[j] > INT32_MAX || !(b[j] >= 0.0) || !std::isfinite(b[j]))
-      return fail(DFMI_ERR_ARG, "lpsd: a plan entry is outside 1 <= L <= N, K >= 1, b >= 0");
-  int rc = ensure_init();
+  double pa;
+  int rc = lpsd_args(N, J, fs, order, psll, b, L, K, x && Sxx && enbw, &pa);
   if (rc) return rc;
+  if ((rc = ensure_init())) return rc;
   hipStream_t st = (hipStream_t)stream;
-
-  // frequencies sorted longest segment first (stable), window rows and tile slots in that order
-  std::vector<int64_t> ord((size_t)J);
-  for (int64_t j = 0; j < J; ++j) ord[(size_t)j] = j;
-  std::stable_sort(ord.begin(), ord.end(), [&](int64_t a, int64_t c) { return L[a] > L[c]; });
-  // one upload: the frequency table, then the 1/k^2 table of lpsd_i0
-  std::vector<double> up((size_t)J * (sizeof(dfmi::LpsdFreq) / 8) + dfmi::kLpsdI0Terms);
-  dfmi::LpsdFreq* hf = (dfmi::LpsdFreq*)up.data();
-  double* hrk2 = up.data() + (size_t)J * (sizeof(dfmi::LpsdFreq) / 8);
-  dfmi::lpsd_fill_rk2(hrk2);
-  const double inv_i0 = 1.0 / dfmi::lpsd_i0(pa, hrk2);
-  int64_t woff = 0, toff = 0;
-  for (int64_t p = 0; p < J; ++p) {
-    const int64_t j = ord[(size_t)p];
-    hf[p] = dfmi::LpsdFreq{b[j], L[j], K[j], woff, toff, j};
-    woff += L[j];
-    toff += K[j];
-  }
-  // batches of consecutive frequencies within the workspace bound
-  const size_t kLpsdBatchBytes = (size_t)t_tune.lpsd_batch_mb << 20;
-  struct Batch { int64_t p0, p1, nw, nt; };
-  std::vector<Batch> batches;
-  size_t max_w = 0, max_t = 0, max_f = 0;
-  for (int64_t p = 0; p < J;) {
-    Batch bt{p, p, 0, 0};
-    while (bt.p1 < J && bt.p1 - bt.p0 < kLpsdBatchFreqs) {
-      const int64_t nw = bt.nw + hf[bt.p1].L, nt = bt.nt + hf[bt.p1].K;
-      if (bt.p1 > bt.p0 && ((size_t)nw + (size_t)nt * (size_t)nser) * 8 > kLpsdBatchBytes) break;
-      bt.nw = nw;
-      bt.nt = nt;
-      ++bt.p1;
-    }
-    if ((size_t)bt.nt > ((size_t)1 << 30)) return fail(DFMI_ERR_UNSUPPORTED, "lpsd: more than 2^30 segments at one frequency");
-    max_w = std::max(max_w, (size_t)bt.nw);
-    max_t = std::max(max_t, (size_t)bt.nt);
-    max_f = std::max(max_f, (size_t)(bt.p1 - bt.p0));
-    batches.push_back(bt);
-    p = bt.p1;
-  }
-  void *dtab, *dwin, *dtile, *dwsum;
-  if ((rc = workspace("lp_tab", up.size() * 8, &dtab))) return rc;
-  if ((rc = workspace("lp_win", max_w * 8, &dwin))) return rc;
-  if ((rc = workspace("lp_tile", max_t * (size_t)nser * 8, &dtile))) return rc;
-  if ((rc = workspace("lp_wsum", max_f * 16, &dwsum))) return rc;
+  LpsdSetup su;
+  if ((rc = lpsd_setup(b, L, K, J, (size_t)nser, pa, st, &su))) return rc;
   Staging sg(mem, st);
   const double* dx = x;
   double *ds, *de;
@@ -2405,21 +2466,48 @@ int dfmi_lpsd(const double* x, int64_t nser, int64_t ser_stride, int64_t N, doub
   }
   if ((rc = sg.out("lp_sxx", Sxx, (size_t)nser * J * 8, &ds))) return rc;
   if ((rc = sg.out("lp_enbw", enbw, (size_t)J * 8, &de))) return rc;
-  // the tables are this call's own host memory: uploaded before the call returns
-  HIPCHK(hipMemcpyAsync(dtab, up.data(), up.size() * 8, hipMemcpyHostToDevice, st));
-  HIPCHK(hipStreamSynchronize(st));
-  const dfmi::LpsdFreq* df = (const dfmi::LpsdFreq*)dtab;
-  const double* drk2 = (const double*)dtab + (size_t)J * (sizeof(dfmi::LpsdFreq) / 8);
-  for (const Batch& bt : batches) {
-    int n256 = 0;
-    int64_t t256 = 0;
-    for (int64_t p = bt.p0; p < bt.p1 && hf[p].L > dfmi::kLpsdWaveL; ++p) {
-      ++n256;
-      t256 += hf[p].K;
-    }
-    HIPCHK(dfmi::lpsd_batch_launch(dx, nser, sg.host ? N : stride, N, fs, df + bt.p0, (int)(bt.p1 - bt.p0),
-                                   n256, hf[bt.p0].L, t256, bt.nt - t256, order, pa, inv_i0, drk2, hf[bt.p0].woff,
-                                   (double*)dwin, (double*)dwsum, hf[bt.p0].toff, bt.nt, (double*)dtile, J, ds, de, st));
+  for (const LpsdSetup::Batch& bt : su.batches) {
+    const dfmi::LpsdFreq& f0 = su.hf[(size_t)bt.p0];
+    HIPCHK(dfmi::lpsd_batch_launch(dx, nser, sg.host ? N : stride, N, fs, su.df + bt.p0, (int)(bt.p1 - bt.p0), bt.n256,
+                                   f0.L, bt.t256, bt.nt - bt.t256, order, pa, su.inv_i0, su.drk2, f0.woff, su.dwin,
+                                   su.dwsum, f0.toff, bt.nt, su.dtile, J, ds, de, st));
+  }
+  return sg.finish();
+}
+
+int dfmi_lcsd(const double* x, int64_t x_stride, const double* y, int64_t y_stride, int64_t npair, int64_t N,
+              double fs, const double* b, const int64_t* L, const int64_t* K, int64_t J, int32_t order, double psll,
+              double* Sxx, double* Syy, double* Sxy_re, double* Sxy_im, double* coh, double* enbw, int32_t mem,
+              void* stream) {
+  CallScope cs(stream);
+  if (npair < 1 || npair > 65535 || N < 1 || N > INT32_MAX || J < 1 || J > INT32_MAX)
+    return fail(DFMI_ERR_ARG, "bad lcsd geometry (1 <= npair <= 65535, 1 <= N < 2^31, J >= 1)");
+  if (x_stride != 0 && npair > 1 && x_stride < N) return fail(DFMI_ERR_ARG, "x_stride < N (0: one x for every y)");
+  if (npair > 1 && y_stride < N) return fail(DFMI_ERR_ARG, "y_stride < N");
+  double pa;
+  int rc = lpsd_args(N, J, fs, order, psll, b, L, K, x && y, &pa);
+  if (rc) return rc;
+  if (!Sxx && !Syy && !Sxy_re && !Sxy_im && !coh)
+    return fail(DFMI_ERR_ARG, "lcsd: at least one of Sxx, Syy, Sxy_re, Sxy_im, coh is required");
+  if ((rc = ensure_init())) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  LpsdSetup su;
+  if ((rc = lpsd_setup(b, L, K, J, (size_t)4 * (size_t)npair, pa, st, &su))) return rc;
+  // the series keep their strides in both memories (host: the rows' whole extent is copied)
+  const int64_t xs = npair > 1 ? x_stride : 0, ys = npair > 1 ? y_stride : 0;
+  Staging sg(mem, st);
+  const double *dx, *dy;
+  if ((rc = sg.in("lc_x", x, (size_t)((xs ? npair - 1 : 0) * xs + N) * 8, &dx))) return rc;
+  if ((rc = sg.in("lc_y", y, (size_t)((npair - 1) * ys + N) * 8, &dy))) return rc;
+  double* out[6] = {Sxx, Syy, Sxy_re, Sxy_im, coh, enbw};
+  static const char* const kName[6] = {"lc_sxx", "lc_syy", "lc_re", "lc_im", "lc_coh", "lc_enbw"};
+  for (int i = 0; i < 6; ++i)
+    if (out[i] && (rc = sg.out(kName[i], out[i], (size_t)(i < 5 ? npair : 1) * J * 8, &out[i]))) return rc;
+  for (const LpsdSetup::Batch& bt : su.batches) {
+    const dfmi::LpsdFreq& f0 = su.hf[(size_t)bt.p0];
+    HIPCHK(dfmi::lcsd_batch_launch(dx, xs, dy, ys, npair, N, fs, su.df + bt.p0, (int)(bt.p1 - bt.p0), bt.n256, f0.L,
+                                   bt.t256, bt.nt - bt.t256, order, pa, su.inv_i0, su.drk2, f0.woff, su.dwin, su.dwsum,
+                                   f0.toff, bt.nt, su.dtile, J, out[0], out[1], out[2], out[3], out[4], out[5], st));
   }
   return sg.finish();
 }

@@ -1,7 +1,8 @@
 // lpsd.h — point functions of the log-frequency spectral density (dfmi_lpsd):
 // the Kaiser window sample, the phasor of a fractional bin and the accumulation of one lane's
 // share of a segment. __host__ __device__, so tests/hostcheck_lpsd runs the same code on the
-// CPU; lpsd.hip holds the kernels.
+// CPU; lpsd.hip holds the kernels. The pair forms at the end (lpsd_share_bin2, lcsd_coherence)
+// are dfmi_lcsd's (host twin tests/hostcheck_lcsd).
 //
 //   w[n] = I0(pi alpha sqrt(1 - z^2)) / I0(pi alpha), z = 2n/L - 1, n = 0..L-1  (DFT-even Kaiser)
 //   alpha = ((0.0889732 p - 0.493285) p + 4.71469) p - 0.0821377, p = psll/100
@@ -106,6 +107,38 @@ DFMI_HDI void lpsd_share_bin(const double* __restrict__ x, const double* __restr
   }
   *re = ar;
   *im = ai;
+}
+
+// The pair form (dfmi_lcsd): one lane's share of A (from x, mean mx) and B (from
+// y, mean my) with one phasor and one window load per sample. Each accumulator sees the
+// expressions of lpsd_share_bin in its order, so A and B are bit for bit what two single calls give.
+DFMI_HDI void lpsd_share_bin2(const double* __restrict__ x, const double* __restrict__ y,
+                              const double* __restrict__ w, int64_t L, double b, double mx, double my, int lane,
+                              int team, double* are, double* aim, double* bre, double* bim) {
+  double ar = 0.0, ai = 0.0, br = 0.0, bi = 0.0;
+  const double Ld = (double)L;
+  for (int64_t n = lane; n < L; n += team) {
+    double c, s;
+    lpsd_phasor(b, n, Ld, &c, &s);
+    const double wn = w[n];
+    const double vx = wn * (x[n] - mx);
+    const double vy = wn * (y[n] - my);
+    ar = fma(vx, c, ar);
+    ai = fma(vx, s, ai);
+    br = fma(vy, c, br);
+    bi = fma(vy, s, bi);
+  }
+  *are = ar;
+  *aim = ai;
+  *bre = br;
+  *bim = bi;
+}
+
+// Magnitude-squared coherence |Sxy|^2 / (Sxx Syy) of one frequency: not clamped (rounding may
+// leave it a few 1e-14 above 1); NaN where Sxx Syy is 0 or NaN.
+DFMI_HDI double lcsd_coherence(double sxx, double syy, double re, double im) {
+  const double den = sxx * syy;
+  return den > 0.0 ? fma(re, re, im * im) / den : NAN;
 }
 
 }  // namespace dfmi

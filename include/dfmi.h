@@ -398,6 +398,27 @@ int dfmi_lpsd(const double* x, int64_t nser, int64_t ser_stride, int64_t N, doub
               const int64_t* L, const int64_t* K, int64_t J, int32_t order, double psll, double* Sxx, double* enbw,
               int32_t mem, void* stream);
 
+/* dfmi_lcsd: the cross-spectral density and magnitude-squared coherence of npair pairs of
+ * series on dfmi_lpsd's plan, window, segment starts and `order` rule.
+ * Pair p is (x + p*x_stride, y + p*y_stride), both of N samples; x_stride == 0 pairs one x with
+ * every y (one witness against many channels), otherwise both strides are >= N when npair > 1
+ * (1 <= npair <= 65535). Per segment, with each series' own segment mean removed at order 0,
+ *   A = sum_n w[n] (x[s+n] - xmean) exp(-2 pi i b n / L),  B the same of y
+ *   Sxx = 2 mean_k |A|^2 / (fs sum w^2)  (dfmi_lpsd's bits),  Syy the same of B
+ *   Sxy = 2 mean_k conj(A) B / (fs sum w^2)  (complex: Sxy_re, Sxy_im; scipy.signal.csd's sign)
+ *   coh = |Sxy|^2 / (Sxx Syy)  (not clamped: rounding may leave it a few 1e-14 above 1; K = 1
+ *         gives 1; NaN where Sxx Syy = 0),   enbw[j] = fs sum w^2 / (sum w)^2
+ * A and B share one phasor and one window load per sample. Outputs are (npair x J) row-major,
+ * enbw has J entries; any output may be NULL (not written), but not all of Sxx, Syy, Sxy_re,
+ * Sxy_im, coh. NaN samples propagate as in dfmi_lpsd. mem, stream, the fixed order of every
+ * sum, the workspaces and "lpsd_batch_mb" (the tiles count 4 npair doubles per segment) are
+ * dfmi_lpsd's. The transfer estimate H = Sxy / Sxx and the residual Syy (1 - coh) are left to
+ * the caller (deepfmkit_amd.lpsd.lcsd). */
+int dfmi_lcsd(const double* x, int64_t x_stride, const double* y, int64_t y_stride, int64_t npair, int64_t N,
+              double fs, const double* b, const int64_t* L, const int64_t* K, int64_t J, int32_t order, double psll,
+              double* Sxx, double* Syy, double* Sxy_re, double* Sxy_im, double* coh, double* enbw,
+              int32_t mem, void* stream);
+
 /* ---- Witness-based fitters (EXPERIMENTAL in the reference) ----
  * Replace, per record (main channel + witness channel):
  *   DFMI_WDFMI_NLS    WDFMI_NLSFitter.fit        fitters.py:481-570 (least_squares(method='lm'))
