@@ -21,6 +21,7 @@ DFMI_MEM_HOST = 0
 DFMI_MEM_DEVICE = 1
 DFMI_F64 = 0  # sample types of the *_typed entry points
 DFMI_F32 = 1
+DFMI_I16 = 3  # int16 counts (2 stays unassigned: an argument error)
 MAX_LAMBDA = 16
 
 SYMBOLS = ("dfmi_lm_config_default", "dfmi_demod", "dfmi_lm", "dfmi_nls_record", "dfmi_ekf",

@@ -100,8 +100,12 @@ class DeepFitFramework:
         """core.py:259-286: one DeepRawObject per channel (column). With `device`
         the samples go straight to that GPU (pinned staging) as the raw's data; with
         dtype="float32" as well they stay there as float32 (parsed as float64, cast once;
-        the NLS fitter reads float32 natively). Without `device` the data is the reference's
-        float64 DataFrame and a dtype is refused."""
+        the NLS fitter reads float32 natively). dtype="int16" is for files of ADC counts: every
+        value must be an integer within [-32768, 32767] (ValueError otherwise); the samples stay
+        on the GPU as int16, the NLS fitter (method 'nls') reads them natively and its amp, dc
+        and init_a are then in counts. Every other method takes float64 data only, as for a
+        float32 device tensor. Without `device` the data is the reference's float64 DataFrame
+        and a dtype is refused."""
         from . import textio
         from .data import DeepRawObject
         if raw_file is not None:

@@ -22,13 +22,15 @@
 // a reduce-scatter butterfly over the 64 lanes (16 values → 17 shuffles per
 // block of 8 harmonics, instead of 16×6).
 //
-// Sample type: the kernels that read samples are templates over XT (SampleT below), double
-// or float; the loads widen in registers and nothing after the load depends on XT. The bin,
-// many-harmonic and seed kernels exist for both; demod_fold_kernel and demod_direct_kernel
-// read doubles only (the host widens another type into a workspace for them).
+// Sample type: the kernels that read samples are templates over XT (SampleT below), double,
+// float or int16_t; the loads widen in registers and nothing after the load depends on XT. The
+// bin, many-harmonic and seed kernels exist for all three; demod_fold_kernel and
+// demod_direct_kernel read doubles only (the host widens another type into a workspace for them).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "dfmi_math.h"
 
@@ -118,13 +120,12 @@ struct VecT<2> {
 
 // Sample-load trait: how the sample-reading device code fetches a record's samples of type
 // XT. Every load returns doubles; a narrower type is widened in registers right after the
-// load (float -> double is exact), so everything downstream of the load — the phase bins,
-// fold_finish, the QI layouts — is the same code for every XT, and a record of XT samples
+// load (float -> double and int16 -> double are exact), so everything downstream of the load
+// — the phase bins, fold_finish, the QI layouts — is the same code for every XT, and a record of XT samples
 // gives the bits the double kernels give on the widened record as long as the bins still
 // receive their samples in ascending t (the lane mapping below is the double one: lane l
-// holds samples 2l, 2l+1 of a 128-sample chunk, an 8-byte load per lane for float).
-// XT = double is the VecT code above, unchanged. Further sample types (integers) are
-// further specialisations.
+// holds samples 2l, 2l+1 of a 128-sample chunk, an 8-byte load per lane for float, a 4-byte
+// load for int16_t). XT = double is the VecT code above, unchanged.
 template <typename XT>
 struct SampleT;
 template <>
@@ -162,6 +163,28 @@ struct SampleT<float> {
       o[0] = (double)v.x;
       o[1] = (double)v.y;
     }
+  }
+};
+
+// 16-bit integer counts (an ADC's or phasemeter's record): the value is the count, widened
+// exactly. The pair load is one 4-byte load per lane (low half = sample 2l, little endian);
+// the two halves are sign-extended and converted in registers.
+template <>
+struct SampleT<int16_t> {
+  __device__ static __forceinline__ double at(const int16_t* p) { return (double)(int)*p; }
+  __device__ static __forceinline__ void widen(int32_t w, double (&o)[2]) {
+    o[0] = (double)(int16_t)w;  // v_bfe_i32 + v_cvt_f64_i32
+    o[1] = (double)(w >> 16);   // arithmetic shift: the high half, sign-extended
+  }
+  template <int VEC>
+  __device__ static __forceinline__ void load(const int16_t* p, double (&o)[VEC]) {
+    if constexpr (VEC == 1) o[0] = (double)(int)*p;
+    else widen(*reinterpret_cast<const int32_t*>(p), o);  // global_load_dword
+  }
+  template <int VEC>
+  __device__ static __forceinline__ void load_nt(const int16_t* p, double (&o)[VEC]) {
+    if constexpr (VEC == 1) o[0] = (double)(int)__builtin_nontemporal_load(p);
+    else widen(__builtin_nontemporal_load(reinterpret_cast<const int32_t*>(p)), o);
   }
 };
 
@@ -555,6 +578,128 @@ __device__ __forceinline__ void bins_segment(const XT* __restrict__ xs0, int R, 
   fold_finish<2, MAXSLOT, HB, ROWS, ROW_LDS>(y, pval, pbase, R, L, ndata, T, lane, qi, qi_ld, col, dc);
 }
 
+// int16 counts folded by INTEGER accumulation. Every partial sum of int16 values is an exact
+// integer (|sum| <= ceil(R / L) · 32768, host-guarded to fit int32), so any order of
+// accumulation gives the bin values the ascending-time float64 fold gives, bit for bit, and
+// the bins need not be the flat-load kernel's LDS bins: lane l keeps fold_finish's own bins
+// p = 2·(l + 64·j) + e (fold_segment's mapping) as int32 in registers, every cycle of L
+// samples is one 4-byte load per lane and slot, sign-extended and added — no LDS
+// read-modify-write, no conversion per sample — and each bin is converted to double once per
+// segment and handed to the unchanged fold_finish. (Cycle-aligned loads reach 5.5 of 6.7 TB/s
+// for float64, above; an int16 record is a quarter of the bytes.) A kernel instantiated for
+// the sample type I16Int (the same int16 counts in memory) folds this way.
+struct I16Int {
+  int16_t v;
+};
+
+// The integer fold's loads carry no lane predicate (a predicated load is a branch around it):
+// a lane whose pair of slot j lies past L reads its slot-0 pair instead (always inside the cycle,
+// L >= 128) and drops it with a mask. poff: the pair's offset in the cycle, pmask: -1 or 0.
+template <int MAXSLOT>
+__device__ __forceinline__ void iacc_lanes(const bool (&pval)[MAXSLOT], const int (&pbase)[MAXSLOT],
+                                           int (&poff)[MAXSLOT], int32_t (&pmask)[MAXSLOT]) {
+#pragma unroll
+  for (int j = 0; j < MAXSLOT; ++j) {
+    poff[j] = pval[j] ? pbase[j] : pbase[0];
+    pmask[j] = pval[j] ? -1 : 0;
+  }
+}
+
+__device__ __forceinline__ int32_t iacc_load(const int16_t* __restrict__ p) {
+  return __builtin_nontemporal_load(reinterpret_cast<const int32_t*>(p));  // global_load_dword ... nt
+}
+
+// The lane's pairs of PFN cycles of the segment at xs (PFN <= R / L), in flight.
+template <int MAXSLOT, int PFN>
+__device__ __forceinline__ void iacc_prefetch(const int16_t* __restrict__ xs, int L, const int (&poff)[MAXSLOT],
+                                              int32_t (*pf)[MAXSLOT]) {
+#pragma unroll
+  for (int u = 0; u < PFN; ++u)
+#pragma unroll
+    for (int j = 0; j < MAXSLOT; ++j) pf[u][j] = iacc_load(xs + u * L + poff[j]);
+}
+
+// bins_segment for I16Int: one segment folded into the lane's int32 bins, then fold_finish.
+// PFN > 0: the first PFN cycles arrive prefetched in pf (R / L >= PFN) and the next segment's
+// (at `next`, if not null) are issued before the contraction, as bins_segment does with chunks.
+template <int MAXSLOT, int LOADS, int HB, bool ROWS, int PFN = 0, bool ROW_LDS = false>
+__device__ __forceinline__ void bins_segment_iacc(const int16_t* __restrict__ xs, int R, int L, int ndata,
+                                                  const double* __restrict__ T, int lane,
+                                                  const bool (&pval)[MAXSLOT], const int (&pbase)[MAXSLOT],
+                                                  const int (&poff)[MAXSLOT], const int32_t (&pmask)[MAXSLOT],
+                                                  double* __restrict__ qi, int64_t qi_ld, int64_t col,
+                                                  double* __restrict__ dc, int32_t (*pf)[MAXSLOT] = nullptr,
+                                                  const int16_t* __restrict__ next = nullptr) {
+  constexpr int UNR = (MAXSLOT >= LOADS) ? 1 : (LOADS / MAXSLOT);  // cycles per load group
+  const int ncyc = R / L;
+  const int rem = R - ncyc * L;
+  int32_t yi[MAXSLOT][2];
+#pragma unroll
+  for (int j = 0; j < MAXSLOT; ++j) yi[j][0] = yi[j][1] = 0;
+  auto add_pair = [&](int j, int32_t w) {
+    if (j > 0) w &= pmask[j];         // slot 0 is whole (L >= 128)
+    yi[j][0] += (int32_t)(int16_t)w;  // sample 2l: the low half
+    yi[j][1] += w >> 16;              // sample 2l + 1: the high half, sign-extended
+  };
+  int k = 0;
+  if constexpr (PFN > 0) {
+#pragma unroll
+    for (int u = 0; u < PFN; ++u)
+#pragma unroll
+      for (int j = 0; j < MAXSLOT; ++j) add_pair(j, pf[u][j]);
+    k = PFN;
+  }
+  for (; k + UNR <= ncyc; k += UNR) {
+    int32_t v[UNR][MAXSLOT];
+#pragma unroll
+    for (int u = 0; u < UNR; ++u)
+#pragma unroll
+      for (int j = 0; j < MAXSLOT; ++j) v[u][j] = iacc_load(xs + (k + u) * L + poff[j]);
+#pragma unroll
+    for (int u = 0; u < UNR; ++u)
+#pragma unroll
+      for (int j = 0; j < MAXSLOT; ++j) add_pair(j, v[u][j]);
+  }
+  {
+    // the remaining (< UNR) full cycles and the ragged last one as ONE more load group
+    const int left = ncyc - k;  // wave-uniform
+    int32_t v[UNR][MAXSLOT];
+#pragma unroll
+    for (int u = 0; u < UNR; ++u)
+      if (u < left) {
+#pragma unroll
+        for (int j = 0; j < MAXSLOT; ++j) v[u][j] = iacc_load(xs + (k + u) * L + poff[j]);
+      }
+    const int16_t* __restrict__ xr = xs + ncyc * L;  // element-wise (R may be odd)
+    int32_t tv[MAXSLOT][2];
+#pragma unroll
+    for (int j = 0; j < MAXSLOT; ++j)
+#pragma unroll
+      for (int e = 0; e < 2; ++e) tv[j][e] = (pval[j] && pbase[j] + e < rem) ? (int32_t)xr[pbase[j] + e] : 0;
+#pragma unroll
+    for (int u = 0; u < UNR; ++u)
+      if (u < left) {
+#pragma unroll
+        for (int j = 0; j < MAXSLOT; ++j) add_pair(j, v[u][j]);
+      }
+#pragma unroll
+    for (int j = 0; j < MAXSLOT; ++j) {
+      yi[j][0] += tv[j][0];
+      yi[j][1] += tv[j][1];
+    }
+  }
+  if constexpr (PFN > 0) {
+    if (next) iacc_prefetch<MAXSLOT, PFN>(next, L, poff, pf);
+  }
+  double y[MAXSLOT][2];
+#pragma unroll
+  for (int j = 0; j < MAXSLOT; ++j) {
+    y[j][0] = (double)yi[j][0];  // exact; bins of slots past L stayed 0
+    y[j][1] = (double)yi[j][1];
+  }
+  fold_finish<2, MAXSLOT, HB, ROWS, ROW_LDS>(y, pval, pbase, R, L, ndata, T, lane, qi, qi_ld, col, dc);
+}
+
 // One wavefront per segment (grid-stride over 4-wave workgroups that share one LDS
 // copy of the basis); each wave's L bins follow the basis in LDS. LOADS 1-KB chunk
 // loads per lane in flight (non-temporal: the input is read once). ROWS selects the
@@ -592,7 +737,25 @@ __device__ __forceinline__ void bins_kernel_body(
     pval[j] = (j < nslot) && (pbase[j] < L);
   }
   const int64_t s0 = (int64_t)bid * kWavesPerBlock + wave, ds = (int64_t)nwork * kWavesPerBlock;
-  if (PFN > 0 && (R >> 7) >= PFN) {
+  if constexpr (std::is_same<XT, I16Int>::value) {
+    // integer-accumulating fold (bins_segment_iacc): the same pipeline, in cycles
+    const int16_t* __restrict__ xi = reinterpret_cast<const int16_t*>(x);
+    int poff[MAXSLOT];
+    int32_t pmask[MAXSLOT];
+    iacc_lanes<MAXSLOT>(pval, pbase, poff, pmask);
+    if (PFN > 0 && R / L >= PFN) {
+      int32_t pf[PFN > 0 ? PFN : 1][MAXSLOT];
+      if (s0 < nseg) iacc_prefetch<MAXSLOT, PFN>(xi + s0 * seg_stride, L, poff, pf);
+      for (int64_t s = s0; s < nseg; s += ds)
+        bins_segment_iacc<MAXSLOT, LOADS, kHarmBlock, ROWS, PFN>(xi + s * seg_stride, R, L, ndata, lds_dyn, lane, pval,
+                                                                 pbase, poff, pmask, qi, qi_ld, s, dc, pf,
+                                                                 s + ds < nseg ? xi + (s + ds) * seg_stride : nullptr);
+    } else {
+      for (int64_t s = s0; s < nseg; s += ds)
+        bins_segment_iacc<MAXSLOT, LOADS, kHarmBlock, ROWS>(xi + s * seg_stride, R, L, ndata, lds_dyn, lane, pval, pbase,
+                                                            poff, pmask, qi, qi_ld, s, dc);
+    }
+  } else if (PFN > 0 && (R >> 7) >= PFN) {
     // software pipeline across this wave's segments (see bins_segment PFN)
     double pf[PFN > 0 ? PFN : 1][2];
     if (s0 < nseg) {

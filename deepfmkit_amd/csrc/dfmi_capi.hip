@@ -94,6 +94,7 @@ struct Tuning {
                                 // (1: where 7 waves per CU still fit, 2: always, 0: never)
   int demod_wide_rmax = 2000;  // segments shorter than this go through demod_wide_kernel too
   int demod_wide_half = 1;  // demod_wide_kernel: half-wave contraction at 2·ndata + 1 <= 32 (0: off, A/B)
+  int demod_i16_int = 1;    // int16 records: the bin kernels fold by integer accumulation (0: the LDS-bin fold, A/B)
   int demod_wide_dbg = 0;   // diagnostics: demod_wide_kernel without its contraction (1) / stores (2)
   int demod_wide_k = 0;     // demod_wide_kernel segments per wave (KSEG): 0 = 8; 2 / 4 / 8 (A/B)
   int ekf_row = 1;       // EKF: ekf_row_kernel (4 channels per wave) up to ekf_row x 4 x 4 x CUs channels
@@ -581,10 +582,25 @@ thread_local std::string g_last_demod;  // kernel variant of the last demodulati
 
 // Sample types of the typed entry points (dfmi_*_typed): the demodulation and seed launches
 // below are templates over XT; XT = double is the untyped entry points' code. xt_tag: what
-// dfmi_last_demod_kernel appends for a kernel that read XT samples itself.
+// dfmi_last_demod_kernel appends for a kernel that read XT samples itself, xt_widened_tag:
+// for a double kernel that read the "x_widen" copy of them.
 template <typename XT>
 const char* xt_tag() {
-  return std::is_same<XT, float>::value ? " [f32]" : "";
+  return std::is_same<XT, float>::value     ? " [f32]"
+         : std::is_same<XT, int16_t>::value ? " [i16]"
+         : std::is_same<XT, dfmi::I16Int>::value ? " [i16 int]"
+                                                 : "";
+}
+
+// Whether an int16 call of the bin kernels folds by integer accumulation (demod.h I16Int): the
+// tuning key, and bins that cannot overflow int32: ceil(R / L) · 32768 <= 2^31 - 1.
+template <typename XT>
+bool i16_int_fold(int R, int L) {
+  return std::is_same<XT, int16_t>::value && t_tune.demod_i16_int && ((int64_t)R + L - 1) / L <= 65535;
+}
+template <typename XT>
+const char* xt_widened_tag() {
+  return std::is_same<XT, float>::value ? " [f32 widened]" : std::is_same<XT, int16_t>::value ? " [i16 widened]" : "";
 }
 
 // hipOccupancyMaxActiveBlocksPerMultiprocessor, cached per (kernel, LDS bytes): the
@@ -800,6 +816,10 @@ template <typename XT>
 int try_bins(const XT* x, int64_t nseg, int64_t stride, int R, int L, int ndata, const double* tab, double* qi,
              int64_t qi_ld, double* dc, hipStream_t st, int n_cu, bool vec2, size_t lds_cap, bool rows) {
   if (!bins_applicable(vec2, L, ndata, lds_cap)) return 1;
+  if constexpr (std::is_same<XT, int16_t>::value) {
+    if (i16_int_fold<XT>(R, L))
+      return try_bins((const dfmi::I16Int*)x, nseg, stride, R, L, ndata, tab, qi, qi_ld, dc, st, n_cu, vec2, lds_cap, rows);
+  }
   const size_t lds = ((size_t)2 * ndata * L + (size_t)dfmi::kWavesPerBlock * L) * sizeof(double);
   return with_ms((L + 127) / 128, [&](auto ms) {
     constexpr int MS = decltype(ms)::value;
@@ -809,7 +829,7 @@ int try_bins(const XT* x, int64_t nseg, int64_t stride, int R, int L, int ndata,
 }
 
 // Sample pairs loadable as one vector: rows aligned to two samples (16 B for double, 8 B for
-// float) at an even stride, and an even period.
+// float, 4 B for int16_t) at an even stride, and an even period.
 template <typename XT>
 bool vec2_ok(const XT* x, int64_t stride, int L) {
   return (L % 2 == 0) && (stride % 2 == 0) && (((uintptr_t)x & (2 * sizeof(XT) - 1)) == 0);
@@ -818,7 +838,7 @@ bool vec2_ok(const XT* x, int64_t stride, int L) {
 // The typed entry points' fallback for the branches that read doubles only (the fold and
 // direct kernels): nseg rows of R samples widened into the "x_widen" workspace (even row
 // stride, 16-B aligned), followed by the double branch on it; dfmi_last_demod_kernel then
-// ends in " [f32 widened]".
+// ends in " [f32 widened]" / " [i16 widened]".
 template <typename XT>
 int widen_rows(const XT* x, int64_t nseg, int64_t stride, int R, hipStream_t st, const double** out,
                int64_t* out_stride) {
@@ -888,7 +908,7 @@ int demod_device(const XT* x, int64_t nseg, int64_t stride, int R, int ndata, do
         rc = use_lds ? launch_fold_ms<1, true>(ms, xd, nseg, sd, R, L, ndata, tab, qi, qi_ld, dc, st, n_cu)
                      : launch_fold_ms<1, false>(ms, xd, nseg, sd, R, L, ndata, tab, qi, qi_ld, dc, st, n_cu);
       }
-      if (rc == DFMI_OK && !std::is_same<XT, double>::value) g_last_demod += " [f32 widened]";
+      if (rc == DFMI_OK) g_last_demod += xt_widened_tag<XT>();
       return rc;
     }
   }
@@ -904,7 +924,7 @@ int demod_device(const XT* x, int64_t nseg, int64_t stride, int R, int ndata, do
   hipLaunchKernelGGL(dfmi::demod_direct_kernel, dim3((unsigned)grid), dim3(dfmi::kBlockThreads), 0, st, xd, nseg,
                      sd, R, ndata, w0, qi, qi_ld, dc);
   HIPCHK(hipGetLastError());
-  g_last_demod = std::is_same<XT, double>::value ? "demod_direct_kernel" : "demod_direct_kernel [f32 widened]";
+  g_last_demod = std::string("demod_direct_kernel") + xt_widened_tag<XT>();
   return DFMI_OK;
 }
 
@@ -1058,6 +1078,11 @@ int fused_seed_demod(const XT* x, int64_t nrec, int64_t nbuf, int R, int ndata, 
   if (ndata > 16 || L <= 0) return 1;
   const int nslot = (L + 127) / 128;
   if (nslot > 8) return 1;
+  if constexpr (std::is_same<XT, int16_t>::value) {
+    if (i16_int_fold<XT>(R, L))
+      return fused_seed_demod((const dfmi::I16Int*)x, nrec, nbuf, R, ndata, L, tab, rows, qs, gdev, ginl, jtab, c, out,
+                              out_ld, fitok, st);
+  }
   using K = void (*)(const XT*, int64_t, int64_t, int64_t, int, int, int, const double*, double*, int64_t,
                      const double*, dfmi::GuessInline, int, const double*, dfmi::LMConst, double*, int64_t, int64_t,
                      int32_t*, uint64_t*);
@@ -1285,6 +1310,7 @@ const std::map<std::string, Knob>& knobs() {
       {"lm_split", {&Tuning::lm_split, {0, 2, 4}}},
       {"lm_split_from", {&Tuning::lm_split_from, {}}},
       {"demod_wide_half", {&Tuning::demod_wide_half, {0, 1}}},
+      {"demod_i16_int", {&Tuning::demod_i16_int, {0, 1}}},
       {"demod_wide_dbg", {&Tuning::demod_wide_dbg, {0, 1, 2, 3, 4, 5, 6, 7}}},
       {"ekf_row", {&Tuning::ekf_row, {}}},
       {"ekf_rot", {&Tuning::ekf_rot, {0, 1}}},
@@ -1821,7 +1847,7 @@ int nls_record_impl(const XT* x, int64_t nrec, int64_t rec_stride, int64_t nbuf,
 
 
 int bad_xtype(int32_t xtype) {
-  return xtype != DFMI_F64 && xtype != DFMI_F32;
+  return xtype != DFMI_F64 && xtype != DFMI_F32 && xtype != DFMI_I16;
 }
 }  // namespace
 
@@ -1973,6 +1999,8 @@ int dfmi_demod_typed(const void* x, int32_t xtype, int64_t nseg, int64_t seg_str
                      double w0, int32_t period, double* qi, double* dc, int32_t mem, void* stream) {
   if (bad_xtype(xtype)) return fail(DFMI_ERR_ARG, "unknown sample type");
   if (xtype == DFMI_F64) return dfmi_demod((const double*)x, nseg, seg_stride, R, ndata, w0, period, qi, dc, mem, stream);
+  if (xtype == DFMI_I16)
+    return demod_impl<int16_t>((const int16_t*)x, nseg, seg_stride, R, ndata, w0, period, qi, dc, mem, stream);
   return demod_impl<float>((const float*)x, nseg, seg_stride, R, ndata, w0, period, qi, dc, mem, stream);
 }
 
@@ -1985,6 +2013,8 @@ int dfmi_demod_rows_typed(const void* x, int32_t xtype, int64_t nseg, int64_t se
                           double w0, int32_t period, double* rows, int32_t mem, void* stream) {
   if (bad_xtype(xtype)) return fail(DFMI_ERR_ARG, "unknown sample type");
   if (xtype == DFMI_F64) return dfmi_demod_rows((const double*)x, nseg, seg_stride, R, ndata, w0, period, rows, mem, stream);
+  if (xtype == DFMI_I16)
+    return demod_rows_impl<int16_t>((const int16_t*)x, nseg, seg_stride, R, ndata, w0, period, rows, mem, stream);
   return demod_rows_impl<float>((const float*)x, nseg, seg_stride, R, ndata, w0, period, rows, mem, stream);
 }
 
@@ -2003,6 +2033,9 @@ int dfmi_nls_record_typed(const void* x, int32_t xtype, int64_t nrec, int64_t re
   if (xtype == DFMI_F64)
     return dfmi_nls_record((const double*)x, nrec, rec_stride, nbuf, R, ndata, w0, period, init_guess, parallel, nchunk,
                            cfg, out, fitok, mem, stream);
+  if (xtype == DFMI_I16)
+    return nls_record_impl<int16_t>((const int16_t*)x, nrec, rec_stride, nbuf, R, ndata, w0, period, init_guess,
+                                    parallel, nchunk, cfg, out, fitok, mem, stream);
   return nls_record_impl<float>((const float*)x, nrec, rec_stride, nbuf, R, ndata, w0, period, init_guess, parallel,
                                 nchunk, cfg, out, fitok, mem, stream);
 }

@@ -10,7 +10,7 @@
 // shorter than the bulk demodulation.
 //
 // Every seed kernel reads its record's buffer 0 as samples of type XT (demod.h SampleT:
-// double, or float widened on load), so a float record is seeded without a widened copy.
+// double, or float / int16_t widened on load), so such a record is seeded without a widened copy.
 #pragma once
 #include "demod.h"
 #include "lm.h"
@@ -259,8 +259,16 @@ __global__ DFMI_SEED_BOUNDS void demod_seed_bins_kernel(
       pbase[j] = 2 * (lane + 64 * j);
       pval[j] = (j < nslot) && (pbase[j] < L);
     }
-    bins_segment<MAXSLOT, 32, false, kHarmBlock, true, 0, true, XT>(x + r * rec_stride, R, L, ndata, sh, ybin, lane, pval,
-                                                                    pbase, row, 0, 0, nullptr);
+    if constexpr (std::is_same<XT, I16Int>::value) {
+      int poff[MAXSLOT];
+      int32_t pmask[MAXSLOT];
+      iacc_lanes<MAXSLOT>(pval, pbase, poff, pmask);
+      bins_segment_iacc<MAXSLOT, 32, kHarmBlock, true, 0, true>(reinterpret_cast<const int16_t*>(x + r * rec_stride), R,
+                                                                L, ndata, sh, lane, pval, pbase, poff, pmask, row, 0, 0,
+                                                                nullptr);
+    } else
+      bins_segment<MAXSLOT, 32, false, kHarmBlock, true, 0, true, XT>(x + r * rec_stride, R, L, ndata, sh, ybin, lane,
+                                                                      pval, pbase, row, 0, 0, nullptr);
   }
   __syncthreads();
   const uint64_t t_fold = __builtin_amdgcn_s_memrealtime();

@@ -74,11 +74,17 @@ def _on_device(x):
 
 
 def _host_samples(x):
-    """A host record as the library takes it: a float32 array stays float32 (the typed entry
-    point reads it natively: half the bytes over the host link), anything else is widened to
-    float64 as the reference's arithmetic would."""
+    """A host record as the library takes it: a float32 or int16 array stays as it is (the typed
+    entry point reads it natively: a half or a quarter of the bytes over the host link), anything
+    else is widened to float64 as the reference's arithmetic would."""
     x = np.asarray(x)
-    return x if x.dtype == np.float32 else np.asarray(x, dtype=np.float64)
+    return x if x.dtype in (np.float32, np.int16) else np.asarray(x, dtype=np.float64)
+
+
+def _xtype(dtype):
+    """dfmi_*_typed's sample type of a numpy or torch dtype (float64, float32, int16), or None."""
+    return {"float64": _lib.DFMI_F64, "float32": _lib.DFMI_F32, "int16": _lib.DFMI_I16}.get(
+        str(dtype).replace("torch.", ""))
 
 
 def w0_of(f_mod, f_samp):
@@ -114,11 +120,13 @@ def nls_records(records, f_samp, f_mod, R, nbuf, ndata=10, init_guess=(1.6, 6.0,
     """Run the StandardNLSFitter pipeline on one or more equal-length records in ONE
     GPU call (config 3: several channels as one batch).
 
-    records: list of 1-D float64 or float32 arrays (host) or CUDA tensors, or a 2-D array/tensor
-    (nrec, >= nbuf*R). float32 records go to dfmi_nls_record_typed as they are (the kernels widen
-    on load: the same bits as for the widened record); host arrays of any other dtype are widened
-    to float64, device tensors of any other dtype are refused. init_guess: (4,) shared or
-    (nrec, 4). Returns (cols (6, nrec*nbuf) in the order amp, m, phi, psi, dc, ssq; fitok
+    records: list of 1-D float64, float32 or int16 arrays (host) or CUDA tensors, or a 2-D
+    array/tensor (nrec, >= nbuf*R). float32 and int16 records go to dfmi_nls_record_typed as they
+    are (the kernels widen on load: the same bits as for the widened record; a list keeps the
+    type only if every record has it); host arrays of any other dtype are widened to float64,
+    device tensors of any other dtype are refused. An int16 record holds ADC counts and is
+    fitted in count units: amp and dc come back in counts, ssq in counts^2, and init_guess's
+    amplitude is in counts too. init_guess: (4,) shared or (nrec, 4). Returns (cols (6, nrec*nbuf) in the order amp, m, phi, psi, dc, ssq; fitok
     (nrec*nbuf,)), as numpy arrays for host input and as CUDA tensors for device input.
     errors=True: a third value, the (4, nrec*nbuf) standard errors of amp, m, phi, psi
     (_segment_errors; NaN where J^T J at the fitted point has no inverse); ndata >= 3."""
@@ -132,7 +140,7 @@ def nls_records(records, f_samp, f_mod, R, nbuf, ndata=10, init_guess=(1.6, 6.0,
             x = torch.stack([r[: nbuf * R] for r in records]).contiguous()
         else:
             recs = [_host_samples(r) for r in records]
-            dt = np.float32 if all(r.dtype == np.float32 for r in recs) else np.float64
+            dt = recs[0].dtype if all(r.dtype == recs[0].dtype for r in recs) else np.float64
             x = np.ascontiguousarray(np.stack([r[: nbuf * R] for r in recs]), dtype=dt)
     else:
         x = records
@@ -147,9 +155,9 @@ def nls_records(records, f_samp, f_mod, R, nbuf, ndata=10, init_guess=(1.6, 6.0,
     nseg = nrec * nbuf
     if _is_device_tensor(x):
         import torch
-        if x.dtype not in (torch.float64, torch.float32) or x.stride(-1) != 1:
-            raise ValueError("device records must be contiguous float64 or float32 rows")
-        xtype = _lib.DFMI_F32 if x.dtype == torch.float32 else _lib.DFMI_F64
+        xtype = _xtype(x.dtype)
+        if xtype is None or x.stride(-1) != 1:
+            raise ValueError("device records must be contiguous float64, float32 or int16 rows")
         # rows 0..5 of one (7, nseg) block: the six result columns; row 6 receives fitok as
         # int64 (frame_from), so the whole result leaves the device in one copy
         out = torch.empty((7, nseg), dtype=torch.float64, device=x.device)[:6]
@@ -175,8 +183,8 @@ def nls_records(records, f_samp, f_mod, R, nbuf, ndata=10, init_guess=(1.6, 6.0,
         return out, ok
     out = np.empty((6, nseg))
     ok = np.empty(nseg, dtype=np.int32)
-    if x.dtype == np.float32:
-        rc = lib.dfmi_nls_record_typed(_lib.ptr(x), _lib.DFMI_F32, nrec, rec_stride, nbuf, R, ndata, w0, 0,
+    if x.dtype != np.float64:
+        rc = lib.dfmi_nls_record_typed(_lib.ptr(x), _xtype(x.dtype), nrec, rec_stride, nbuf, R, ndata, w0, 0,
                                        _lib.ptr(g), 1 if parallel else 0, max(nchunk, 1), cfg, _lib.ptr(out),
                                        _lib.ptr(ok), _lib.DFMI_MEM_HOST, None)
     else:
@@ -198,7 +206,7 @@ def nls_record_devices(x, f_samp, f_mod, R, nbuf, devices, ndata=10, init_guess=
     fits the seed buffer itself, as every reference Pool chunk receives it (no exchange) —
     and the rows come back in record order. All devices' work is enqueued before any result
     is read, so the GPUs run concurrently; each shard's samples go host -> device (or
-    device -> device) once. x: 1-D float64 or float32 numpy array or CUDA tensor (>= nbuf*R
+    device -> device) once. x: 1-D float64, float32 or int16 numpy array or CUDA tensor (>= nbuf*R
     samples); the shards are allocated in the record's dtype.
     Returns (cols (6, nbuf) numpy in the order amp, m, phi, psi, dc, ssq; fitok (nbuf,)),
     bit-identical to one nls_records call (segments are independent once the seed is known).
@@ -219,7 +227,7 @@ def nls_record_devices(x, f_samp, f_mod, R, nbuf, devices, ndata=10, init_guess=
     host = not _is_device_tensor(x)
     if host:
         x = _host_samples(x)
-    xdt = torch.float32 if x.dtype == (np.float32 if host else torch.float32) else torch.float64
+    xdt = {_lib.DFMI_F32: torch.float32, _lib.DFMI_I16: torch.int16}.get(_xtype(x.dtype), torch.float64)
     pending = []
     for dev, idx in zip(devs, parts):
         b0, b1 = (int(idx[0]), int(idx[-1]) + 1) if idx.size else (1, 1)

@@ -79,13 +79,14 @@ def read_raw(path, device=None, dtype=None):
     """load_raw's data (core.py:279-280): channel c = column c of every row after the
     13 header lines, pandas sep=' ' semantics. Returns (header dict, list of channel
     arrays); with `device` ("cuda:0", ...) the channels are torch tensors there, float64
-    or, with dtype="float32" (only valid together with `device`), cast once to float32 on
-    the host before the copy."""
+    or, with dtype="float32" or "int16" (only valid together with `device`), cast once on the
+    host before the copy. dtype="int16" is for files of ADC counts: every parsed value must be an
+    integer within [-32768, 32767], otherwise a ValueError names the first sample that is not."""
     if dtype is not None:
         if hasattr(dtype, "is_floating_point"):  # a torch dtype: by its name
             dtype = str(dtype).split(".")[-1]
-        if np.dtype(dtype) not in (np.dtype(np.float32), np.dtype(np.float64)):
-            raise ValueError(f"dtype must be float32 or float64, got {dtype!r}")
+        if np.dtype(dtype) not in (np.dtype(np.float32), np.dtype(np.float64), np.dtype(np.int16)):
+            raise ValueError(f"dtype must be float32, float64 or int16, got {dtype!r}")
         if device is None:
             raise ValueError("dtype is only valid together with device (host data stays float64)")
     hdr = parse_header(path, RAW)
@@ -95,6 +96,13 @@ def read_raw(path, device=None, dtype=None):
     import torch
     if dtype is not None and np.dtype(dtype) == np.float32:
         data = data.astype(np.float32)
+    elif dtype is not None and np.dtype(dtype) == np.int16:
+        bad = ~((data >= -32768.0) & (data <= 32767.0) & (data == np.rint(data)))  # NaN: bad
+        if bad.any():
+            c, i = (int(v) for v in np.argwhere(bad.T)[0][::-1])  # first in file order: by row
+            raise ValueError(f"dtype='int16': channel {c}, sample {i} is {data[c, i]!r}, "
+                             "not an integer within [-32768, 32767]")
+        data = data.astype(np.int16)
     host = torch.from_numpy(data).pin_memory()
     dev = host.to(device, non_blocking=True)
     torch.cuda.current_stream(dev.device).synchronize()

@@ -138,24 +138,38 @@ int dfmi_nls_record(const double* x, int64_t nrec, int64_t rec_stride, int64_t n
 
 /* Typed sample input. dfmi_demod_typed, dfmi_demod_rows_typed and dfmi_nls_record_typed are
  * dfmi_demod, dfmi_demod_rows and dfmi_nls_record with the samples x of type `xtype`:
- *   DFMI_F64   double: forwards to the untyped function (same kernel, same bits)
- *   DFMI_F32   float:  the kernels load float and widen in registers
+ *   DFMI_F64   double:  forwards to the untyped function (same kernel, same bits)
+ *   DFMI_F32   float:   the kernels load float and widen in registers
+ *   DFMI_I16   int16_t: ADC / phasemeter counts; the kernels load the counts and widen them
+ *                       in registers. The samples are the counts themselves: there is no
+ *                       scale or offset argument, results are in count units (amp and dc in
+ *                       counts, ssq in counts^2; the init_guess amplitude is in counts too)
  * Every other argument, the outputs (float64) and the layouts are those of the untyped
  * function; strides are in ELEMENTS of the sample type. An unknown xtype is DFMI_ERR_ARG.
- * float -> double is exact and every phase bin still receives its samples in ascending time,
- * so a float record gives, bit for bit, what the untyped function gives on the same record
- * widened to double. With DFMI_MEM_HOST the record is staged and copied as float (half the
- * bytes over the host link); it is never widened on the host.
- * The bin, fused seed + bin, many-harmonic and seed kernels read float themselves; their
- * vector-pair precondition is rows aligned to 8 B at an even stride (16 B for double). The
- * branches left (the fold kernel: L < 128, odd L or rows without pair alignment; the direct
- * kernel) widen the rows into a device workspace of 8 B per sample first and run the double
- * kernel on it. dfmi_last_demod_kernel() says which: the double call's string followed by
- * " [f32]" (read natively) or " [f32 widened]" (the fallback).
+ * float -> double and int16 -> double are exact and every phase bin still receives its
+ * samples in ascending time, so a float or int16 record gives, bit for bit, what the untyped
+ * function gives on the same record widened to double (QI, dc, the six result columns and
+ * fitok). With DFMI_MEM_HOST the record is staged and copied in its own type (a half or a
+ * quarter of the bytes over the host link); it is never widened on the host.
+ * The bin, fused seed + bin, many-harmonic and seed kernels read float and int16 themselves;
+ * their vector-pair precondition is rows aligned to two samples at an even stride (4 B for
+ * int16, 8 B for float, 16 B for double). The branches left (the fold kernel: L < 128, odd L
+ * or rows without pair alignment; the direct kernel) widen the rows into a device workspace
+ * of 8 B per sample first and run the double kernel on it. dfmi_last_demod_kernel() says
+ * which: the double call's string followed by " [f32]" / " [i16]" (read natively) or
+ * " [f32 widened]" / " [i16 widened]" (the fallback).
+ * The bin kernels (bin, fused seed + bin) fold an int16 record by INTEGER accumulation: int32
+ * phase bins in the lanes' registers, each converted to double once per segment — the same
+ * bits, since every partial sum of int16 values is exact in either type — reported as
+ * " [i16 int]". It runs where the bins cannot overflow, ceil(R / period) <= 65535 (a bin's
+ * magnitude is at most ceil(R / period) * 32768 <= 2^31 - 1); a longer segment, or the tuning
+ * key "demod_i16_int" = 0, takes the float kernels' fold on the widened-in-register counts
+ * (" [i16]").
  * Float64 only: dfmi_ekf, dfmi_ekf_fit, dfmi_wdfmi_fit (main and witness records),
  * dfmi_record_moments, and the synthesis calls' outputs (dfmi_synth_asd, dfmi_synth_snr). */
 #define DFMI_F64 0
 #define DFMI_F32 1
+#define DFMI_I16 3
 int dfmi_demod_typed(const void* x, int32_t xtype, int64_t nseg, int64_t seg_stride, int32_t R, int32_t ndata,
                      double w0, int32_t period, double* qi, double* dc, int32_t mem, void* stream);
 int dfmi_demod_rows_typed(const void* x, int32_t xtype, int64_t nseg, int64_t seg_stride, int32_t R, int32_t ndata,
@@ -468,6 +482,8 @@ int dfmi_wdfmi_fit(const double* x, int64_t nrec, int64_t rec_stride, int64_t nb
  * bin / fold kernels; 2: demod_wide_kernel wherever its geometry applies; QI within ~1e-14
  * relative of the bin kernel's), "demod_wide_k" (segments per wave, 0 = 8; 2 / 4 / 8),
  * "demod_wide_half" (1 [default]: half-wave contraction at 2 ndata + 1 <= 32; same bits),
+ * "demod_i16_int" (1 [default]: int16 records fold by integer accumulation in the bin kernels;
+ * 0: the float kernels' fold; same bits),
  * "demod_wide_dbg" (diagnostics: bit 0 no contraction, bit 1 no stores, bit 2 segment-by-segment
  * fold — results invalid with bits 0 / 1), "ekf_row" (EKF row kernel up to ekf_row x 16 x CUs channels, 0 = lane
  * kernel only), "ekf_rot" (1 [default]: the row kernel takes sin / cos by rotation between
@@ -595,9 +611,9 @@ const char* dfmi_version(void);
  * build), e.g. "demod_seed_bins_kernel<2,12,4,10> (prefetch 4)" (the record pipeline's
  * fused seed + demodulation), "demod_bins_kernel<2,10,rows,4> (prefetch 4)" (dfmi_demod_rows),
  * "ekf_rot_kernel", "ekf_row_kernel", "ekf_lane_rot_kernel", "ekf_kernel" ("" before the
- * first one). A typed call on float samples appends " [f32]" when the kernel read them
- * itself and " [f32 widened]" when the rows were widened into a workspace first; float64
- * calls report the plain string. Diagnostics/profiling. */
+ * first one). A typed call on float (int16) samples appends " [f32]" (" [i16]", or " [i16 int]"
+ * for the integer-accumulating fold) when the kernel read them itself and " [f32 widened]" (" [i16 widened]") when the rows were widened
+ * into a workspace first; float64 calls report the plain string. Diagnostics/profiling. */
 const char* dfmi_last_demod_kernel(void);
 
 #ifdef __cplusplus

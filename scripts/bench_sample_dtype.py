@@ -1,7 +1,14 @@
-"""float32 against float64 sample records on the headline step: config 2 (100k segments x
-R = 4000 @ 200 kS/s) at ndata 10, 30 and 62, the SAME values as float64 and as float32
+"""float32 and int16 against float64 sample records on the headline step: config 2 (100k
+segments x R = 4000 @ 200 kS/s) at ndata 10, 30 and 62, the SAME values as float64 and as float32
 (the record is generated, cast to float32 once, and the float64 copy is that cast widened
 back, so both dtypes fit the same numbers and their results must be equal bit for bit).
+The int16 rows fit the same record quantised as a 12-bit-scale ADC would,
+clamp(round(4096 x), -32768, 32767), from an amplitude guess of 1.6 * 4096 counts and with
+FITOK_THRESHOLD stated in counts^2 (1e-3 * 4096^2: ssq is in counts^2, and at the volts-scale
+threshold every segment would take the m-grid retry, a different LM workload), and are
+compared bit for bit with one (untimed) float64 call on the widened counts: "int16" is the
+default path, "int16-ldsbins" the same call with the tuning key demod_i16_int = 0 (the
+float kernels' LDS-bin fold instead of the integer-accumulating fold of the bin kernels).
 
 Device-resident (timed as bench.py times its step: warm-up, then HIP events over --steps
 whole dfmi_nls_record(_typed) calls, repeated --runs times; dfmi_step_timing gives the
@@ -12,7 +19,7 @@ DFMI_MEM_HOST, PCIe-inclusive, as scripts/bench_host_input.py). One JSON line pe
 Copied into a checkout from before the typed entry points, the script times that tree's
 float64 points only (--tag names the tree in the output lines).
 usage: python scripts/bench_sample_dtype.py [--tag NAME] [--ndata 10,30,62] [--steps 20] [--warmup 5]
-                                            [--runs 3] [--no-host]"""
+                                            [--runs 3] [--no-host] [--dtypes float64,float32,int16,int16-ldsbins]"""
 import argparse
 import json
 import os
@@ -38,6 +45,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--no-host", action="store_true")
+    ap.add_argument("--dtypes", default="float64,float32,int16,int16-ldsbins")
     args = ap.parse_args()
 
     import torch
@@ -58,18 +66,37 @@ def main():
     synth_snr(SnrSpec(seed=1234, f_samp=F_SAMP, f_mod=F_MOD, m=6.0, snr_db=40.0), 0, nseg * R, out=x)
     x32 = x.float()
     x64 = x32.double()
+    i16 = typed and hasattr(_lib, "DFMI_I16")  # a tree from before int16 records: the float points only
+    x16 = torch.clamp(torch.round(4096.0 * x), -32768, 32767).to(torch.int16) if i16 else None
     del x
+    want = args.dtypes.split(",")
+    # name -> (samples, sample type or None for the untyped call, demod_i16_int, scale of amp and sqrt(ssq))
+    variants = [("float64", x64, None, None, 1.0)]
+    if typed:
+        variants.append(("float32", x32, _lib.DFMI_F32, None, 1.0))
+    if i16:
+        variants += [("int16", x16, _lib.DFMI_I16, 1, 4096.0), ("int16-ldsbins", x16, _lib.DFMI_I16, 0, 4096.0)]
+    variants = [v for v in variants if v[0] in want]
     w0 = w0_of(F_MOD, F_SAMP)
+    thr0 = F.FITOK_THRESHOLD
     cfg = F.lm_config()
     g = np.array([[1.6, 6.0, 0.0, 0.0]])
+
+    def select(scale, key):
+        nonlocal cfg
+        g[0, 0] = 1.6 * scale
+        F.FITOK_THRESHOLD = thr0 * scale ** 2
+        cfg = F.lm_config()
+        if key is not None:
+            _lib.check(lib.dfmi_set_tuning(b"demod_i16_int", key), "dfmi_set_tuning")
     stream = torch.cuda.current_stream()
     st = stream.cuda_stream
     out = torch.empty((6, nseg), dtype=torch.float64, device=dev)
     ok = torch.empty(nseg, dtype=torch.int32, device=dev)
 
-    def record_call(xp, f32, nd, o, k, mem):
-        if f32:
-            rc = lib.dfmi_nls_record_typed(xp, _lib.DFMI_F32, 1, nseg * R, nseg, R, nd, w0, 0, _lib.ptr(g), 1, nseg - 1,
+    def record_call(xp, xtype, nd, o, k, mem):
+        if xtype is not None:
+            rc = lib.dfmi_nls_record_typed(xp, xtype, 1, nseg * R, nseg, R, nd, w0, 0, _lib.ptr(g), 1, nseg - 1,
                                            cfg, o, k, mem, st if mem == _lib.DFMI_MEM_DEVICE else None)
         else:
             rc = lib.dfmi_nls_record(xp, 1, nseg * R, nseg, R, nd, w0, 0, _lib.ptr(g), 1, nseg - 1, cfg, o, k, mem,
@@ -80,17 +107,22 @@ def main():
     for nd in [int(v) for v in args.ndata.split(",")]:
         qi = torch.empty((2 * nd, nseg), dtype=torch.float64, device=dev)
         dc = torch.empty(nseg, dtype=torch.float64, device=dev)
-        for name, xt in (("float64", x64), ("float32", x32)):
-            f32 = name == "float32"
-            if f32 and not typed:
-                continue
+        for name, xt, xtype, key, scale in variants:
+            select(scale, key)
+            if name == "int16" or (name == "int16-ldsbins" and (nd, "counts") not in results):
+                # the comparand of the int16 rows: the float64 fit of the widened counts, untimed
+                xw = xt.double()
+                record_call(xw.data_ptr(), None, nd, out.data_ptr(), ok.data_ptr(), _lib.DFMI_MEM_DEVICE)
+                torch.cuda.synchronize()
+                results[(nd, "counts")] = (out.cpu().numpy().copy(), ok.cpu().numpy().copy())
+                del xw
 
             def step():
-                record_call(xt.data_ptr(), f32, nd, out.data_ptr(), ok.data_ptr(), _lib.DFMI_MEM_DEVICE)
+                record_call(xt.data_ptr(), xtype, nd, out.data_ptr(), ok.data_ptr(), _lib.DFMI_MEM_DEVICE)
 
             def demod_only():
-                if f32:
-                    rc = lib.dfmi_demod_typed(xt.data_ptr(), _lib.DFMI_F32, nseg, R, R, nd, w0, 0, qi.data_ptr(),
+                if xtype is not None:
+                    rc = lib.dfmi_demod_typed(xt.data_ptr(), xtype, nseg, R, R, nd, w0, 0, qi.data_ptr(),
                                               dc.data_ptr(), _lib.DFMI_MEM_DEVICE, st)
                 else:
                     rc = lib.dfmi_demod(xt.data_ptr(), nseg, R, R, nd, w0, 0, qi.data_ptr(), dc.data_ptr(),
@@ -143,8 +175,9 @@ def main():
                     "demod_kernel": best.get("demod_kernel", kname), "demod_algorithmic_bytes": bytes_demod,
                     "demod_GBps": round(bytes_demod / (best["demod_ms"] * 1e-3) / 1e9, 1),
                     "demod_frac_of_8TBps": round(bytes_demod / (best["demod_ms"] * 1e-3) / HBM_PEAK, 4)}
-            if f32 and (nd, "float64") in results:
-                a, b = results[(nd, "float64")], results[(nd, "float32")]
+            ref = (nd, "float64") if name == "float32" else (nd, "counts") if name.startswith("int16") else None
+            if ref in results:
+                a, b = results[ref], results[(nd, name)]
                 line["equal_to_float64_bits"] = bool(np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]))
             print(json.dumps(line), flush=True)
         del qi, dc
@@ -152,16 +185,14 @@ def main():
     if args.no_host:
         return
     nd = 10
-    for name, xt in (("float64", x64), ("float32", x32)):
-        f32 = name == "float32"
-        if f32 and not typed:
-            continue
+    for name, xt, xtype, key, scale in variants:
+        select(scale, key)
         xh = xt.cpu().pin_memory()
         oh = np.empty((6, nseg))
         kh = np.empty(nseg, dtype=np.int32)
 
         def call():
-            record_call(xh.data_ptr(), f32, nd, _lib.ptr(oh), _lib.ptr(kh), _lib.DFMI_MEM_HOST)
+            record_call(xh.data_ptr(), xtype, nd, _lib.ptr(oh), _lib.ptr(kh), _lib.DFMI_MEM_HOST)
 
         call()
         ts = []
