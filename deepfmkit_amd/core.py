@@ -132,6 +132,26 @@ class DeepFitFramework:
             raw.f_mod = self.f_mod
             self.raws[raw.label] = raw
 
+    def load_frames(self, frames, f_samp, f_mod, labels=None, t0=0):
+        """Frame-interleaved samples as a digitiser delivers them: a 2-D (N, nch) numpy array or
+        CUDA tensor with stride(1) == 1, row t = sample t of every channel. Registers one
+        DeepRawObject per channel whose data is the column view frames[:, c] (no copy); fit_many
+        over all the labels, in order, then fits the frames as they lie (fitters.nls_frames)."""
+        from .data import DeepRawObject
+        if frames.ndim != 2:
+            raise ValueError("frames must be 2-D (samples, channels)")
+        nch = int(frames.shape[1])
+        if labels is None:
+            labels = ["frames_ch" + str(c) for c in range(nch)]
+        else:
+            assert len(labels) == nch
+        for c in range(nch):
+            raw = DeepRawObject()
+            raw.data = frames[:, c]
+            raw.label, raw.t0, raw.f_samp, raw.f_mod = labels[c], t0, f_samp, f_mod
+            self.raws[raw.label] = raw
+        return list(labels)
+
     def load_fit(self, fit_file=None, labels=None):
         """core.py:288-332 (labels default to <raw_file>_ch<c>, as the reference: a
         framework without a raw file raises the same TypeError)."""
@@ -352,12 +372,17 @@ class DeepFitFramework:
             raise ValueError(f"cannot reshape array of size {N} into shape ({R})")
         parallel = kwargs.get("parallel", True)
         g = (kwargs.get("init_a", 1.6), kwargs.get("init_m", 6.0), 0.0, kwargs.get("init_psi", 0.0))
+        # the columns of one frames block (load_frames), all of them in order: fitted as they lie
+        recs = [r.samples() for r in raws]
+        frames = _fitters.frames_of(recs)
+        fit_records = _fitters.nls_records if frames is None else _fitters.nls_frames
+        recs = recs if frames is None else frames
         if kwargs.get("errors"):
-            df_all = _fitters.frame_with_errors(*_fitters.nls_records(
-                [r.samples() for r in raws], r0.f_samp, r0.f_mod, R, nbuf, ndata, g, parallel=parallel,
+            df_all = _fitters.frame_with_errors(*fit_records(
+                recs, r0.f_samp, r0.f_mod, R, nbuf, ndata, g, parallel=parallel,
                 n_cores=kwargs.get("n_cores") if parallel else None, errors=True))
         else:
-            cols, ok = _fitters.nls_records([r.samples() for r in raws], r0.f_samp, r0.f_mod, R, nbuf, ndata, g,
+            cols, ok = fit_records(recs, r0.f_samp, r0.f_mod, R, nbuf, ndata, g,
                                             parallel=parallel, n_cores=kwargs.get("n_cores") if parallel else None)
             df_all = _fitters.frame_from(cols, ok)
         for i, (l, raw) in enumerate(zip(labels, raws)):

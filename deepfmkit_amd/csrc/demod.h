@@ -794,6 +794,197 @@ __global__ __launch_bounds__(kBlockThreads) void demod_bins_kernel(
   bins_kernel_body<MAXSLOT, LOADS, ROWS, PFN, XT>(x, nseg, seg_stride, R, L, ndata, tab, qi, qi_ld, dc, probe);
 }
 
+// Frame-interleaved int16 records: x[(b·R + t)·NCH + c], sample t of every channel side by side
+// (what a digitiser delivers), folded without de-interleaving. The integer fold above makes the
+// order of accumulation free, so one wave takes a buffer's frames as they lie and keeps one set
+// of int32 bins per channel: lane l, slot j owns bins p = 2·(l + 64·j) + e of EVERY channel, and
+// the two frames of those bins are 2·NCH int16 = 4·NCH contiguous bytes — one global_load_dwordx2
+// (NCH 2), one dwordx4 (NCH 4) or two dwordx4 (NCH 8) per lane, slot and cycle, non-temporal; a
+// wave-wide load is one contiguous run of 512 / 1024 / 2048 B and every line of the record is
+// read once, by one wave. Dword i of the group holds frame e = i / (NCH/2), channels
+// 2·(i mod NCH/2) (low half) and 2·(i mod NCH/2) + 1 (high half): static per NCH, so the
+// unpacking is one sign extension and one arithmetic shift per dword with no dynamic index into
+// the bins. Lanes whose pair of slot j lies past L re-read their slot-0 frames and mask them
+// (iacc_lanes). Each channel's bins are then converted to double (exact) and handed to the
+// unchanged fold_finish with column c·nbuf + b: the bits of the planar integer fold on the
+// de-interleaved record.
+// Preconditions (host-checked): 128 <= L <= 128·MAXSLOT, L and R even, ceil(R / L) <= 65535,
+// x aligned to min(4·NCH, 16) bytes (with R even every buffer and every load then is), the
+// basis in LDS.
+template <int NCH>
+__device__ __forceinline__ void frames_load(const int16_t* __restrict__ p, int32_t (&w)[NCH]) {
+  typedef int32_t i2v __attribute__((ext_vector_type(2)));
+  typedef int32_t i4v __attribute__((ext_vector_type(4)));
+  if constexpr (NCH == 2) {
+    const i2v v = __builtin_nontemporal_load(reinterpret_cast<const i2v*>(p));  // global_load_dwordx2 ... nt
+    w[0] = v.x;
+    w[1] = v.y;
+  } else {
+#pragma unroll
+    for (int q = 0; q < NCH / 4; ++q) {
+      const i4v v = __builtin_nontemporal_load(reinterpret_cast<const i4v*>(p) + q);  // global_load_dwordx4 ... nt
+      w[4 * q] = v.x;
+      w[4 * q + 1] = v.y;
+      w[4 * q + 2] = v.z;
+      w[4 * q + 3] = v.w;
+    }
+  }
+}
+
+// The two frames of one lane and slot added into the bins of their channels and parities.
+template <int NCH, int MAXSLOT>
+__device__ __forceinline__ void frames_add(int32_t (&yi)[NCH][MAXSLOT][2], int j, const int32_t (&w)[NCH],
+                                           int32_t mask) {
+#pragma unroll
+  for (int i = 0; i < NCH; ++i) {
+    const int e = i / (NCH / 2), c = 2 * (i % (NCH / 2));
+    const int32_t v = w[i] & mask;
+    yi[c][j][e] += (int32_t)(int16_t)v;  // channel c: the low half
+    yi[c + 1][j][e] += v >> 16;          // channel c + 1: the high half, sign-extended
+  }
+}
+
+// The lane's frame pairs of PFN cycles of the buffer at xs (PFN <= R / L), in flight.
+template <int NCH, int MAXSLOT, int PFN>
+__device__ __forceinline__ void frames_prefetch(const int16_t* __restrict__ xs, int L, const int (&poff)[MAXSLOT],
+                                                int32_t (*pf)[MAXSLOT][NCH]) {
+#pragma unroll
+  for (int u = 0; u < PFN; ++u)
+#pragma unroll
+    for (int j = 0; j < MAXSLOT; ++j) frames_load<NCH>(xs + (u * L + poff[j]) * NCH, pf[u][j]);
+}
+
+// One buffer of NCH channels (R frames at xs): bins_segment_iacc with NCH bin sets. LOADS wide
+// loads per lane in flight (LOADS / MAXSLOT cycles a group); PFN as in bins_segment_iacc.
+template <int NCH, int MAXSLOT, int LOADS, bool ROWS, int PFN>
+__device__ __forceinline__ void frames_segment(const int16_t* __restrict__ xs, int R, int L, int ndata,
+                                               const double* __restrict__ T, int lane, const bool (&pval)[MAXSLOT],
+                                               const int (&pbase)[MAXSLOT], const int (&poff)[MAXSLOT],
+                                               const int32_t (&pmask)[MAXSLOT], double* __restrict__ qi,
+                                               int64_t qi_ld, int64_t b, int64_t nbuf, double* __restrict__ dc,
+                                               int32_t (*pf)[MAXSLOT][NCH] = nullptr,
+                                               const int16_t* __restrict__ next = nullptr) {
+  constexpr int UNR = (MAXSLOT >= LOADS) ? 1 : (LOADS / MAXSLOT);  // cycles per load group
+  const int ncyc = R / L;
+  const int rem = R - ncyc * L;
+  int32_t yi[NCH][MAXSLOT][2];
+#pragma unroll
+  for (int c = 0; c < NCH; ++c)
+#pragma unroll
+    for (int j = 0; j < MAXSLOT; ++j) yi[c][j][0] = yi[c][j][1] = 0;
+  int k = 0;
+  if constexpr (PFN > 0) {
+#pragma unroll
+    for (int u = 0; u < PFN; ++u)
+#pragma unroll
+      for (int j = 0; j < MAXSLOT; ++j) frames_add<NCH, MAXSLOT>(yi, j, pf[u][j], pmask[j]);
+    k = PFN;
+  }
+  for (; k + UNR <= ncyc; k += UNR) {
+    int32_t v[UNR][MAXSLOT][NCH];
+#pragma unroll
+    for (int u = 0; u < UNR; ++u)
+#pragma unroll
+      for (int j = 0; j < MAXSLOT; ++j) frames_load<NCH>(xs + ((k + u) * L + poff[j]) * NCH, v[u][j]);
+#pragma unroll
+    for (int u = 0; u < UNR; ++u)
+#pragma unroll
+      for (int j = 0; j < MAXSLOT; ++j) frames_add<NCH, MAXSLOT>(yi, j, v[u][j], pmask[j]);
+  }
+  for (; k < ncyc; ++k) {  // the remaining (< UNR) full cycles
+    int32_t v[MAXSLOT][NCH];
+#pragma unroll
+    for (int j = 0; j < MAXSLOT; ++j) frames_load<NCH>(xs + (k * L + poff[j]) * NCH, v[j]);
+#pragma unroll
+    for (int j = 0; j < MAXSLOT; ++j) frames_add<NCH, MAXSLOT>(yi, j, v[j], pmask[j]);
+  }
+  if (rem) {  // the ragged last cycle, element-wise per channel (wave-uniform branch)
+    const int16_t* __restrict__ xr = xs + ncyc * L * NCH;
+#pragma unroll
+    for (int j = 0; j < MAXSLOT; ++j)
+#pragma unroll
+      for (int e = 0; e < 2; ++e)
+        if (pval[j] && pbase[j] + e < rem) {
+#pragma unroll
+          for (int c = 0; c < NCH; ++c) yi[c][j][e] += (int32_t)xr[(pbase[j] + e) * NCH + c];
+        }
+  }
+  if constexpr (PFN > 0) {
+    if (next) frames_prefetch<NCH, MAXSLOT, PFN>(next, L, poff, pf);
+  }
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    double y[MAXSLOT][2];
+#pragma unroll
+    for (int j = 0; j < MAXSLOT; ++j) {
+      y[j][0] = (double)yi[c][j][0];  // exact; bins of slots past L stayed 0
+      y[j][1] = (double)yi[c][j][1];
+    }
+    fold_finish<2, MAXSLOT, kHarmBlock, ROWS>(y, pval, pbase, R, L, ndata, T, lane, qi, qi_ld, c * nbuf + b, dc);
+  }
+}
+
+// One wave per buffer index b (grid-stride over the nbuf buffers), four-wave workgroups sharing
+// one LDS copy of the basis; a wave folds all NCH channels of its buffer.
+template <int NCH, int MAXSLOT, int LOADS, bool ROWS, int PFN>
+__global__ __launch_bounds__(kBlockThreads) void demod_frames_kernel(
+    const int16_t* __restrict__ x, int64_t nbuf, int R, int L, int ndata, const double* __restrict__ tab,
+    double* __restrict__ qi, int64_t qi_ld, double* __restrict__ dc) {
+  static_assert(NCH == 2 || NCH == 4 || NCH == 8, "NCH");
+  extern __shared__ __attribute__((aligned(16))) double lds_dyn[];
+  stage_table(tab, lds_dyn, 2 * ndata * L, threadIdx.x, kBlockThreads);
+  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int nslot = (L + 127) / 128;
+  int pbase[MAXSLOT], poff[MAXSLOT];
+  bool pval[MAXSLOT];
+  int32_t pmask[MAXSLOT];
+#pragma unroll
+  for (int j = 0; j < MAXSLOT; ++j) {
+    pbase[j] = 2 * (lane + 64 * j);
+    pval[j] = (j < nslot) && (pbase[j] < L);
+  }
+  iacc_lanes<MAXSLOT>(pval, pbase, poff, pmask);
+  const int64_t bstride = (int64_t)R * NCH;  // int16 elements per buffer
+  const int64_t b0 = (int64_t)blockIdx.x * kWavesPerBlock + wave, db = (int64_t)gridDim.x * kWavesPerBlock;
+  if (R / L >= PFN) {
+    int32_t pf[PFN][MAXSLOT][NCH];
+    if (b0 < nbuf) frames_prefetch<NCH, MAXSLOT, PFN>(x + b0 * bstride, L, poff, pf);
+    for (int64_t b = b0; b < nbuf; b += db)
+      frames_segment<NCH, MAXSLOT, LOADS, ROWS, PFN>(x + b * bstride, R, L, ndata, lds_dyn, lane, pval, pbase, poff,
+                                                     pmask, qi, qi_ld, b, nbuf, dc, pf,
+                                                     b + db < nbuf ? x + (b + db) * bstride : nullptr);
+  } else {
+    for (int64_t b = b0; b < nbuf; b += db)
+      frames_segment<NCH, MAXSLOT, LOADS, ROWS, 0>(x + b * bstride, R, L, ndata, lds_dyn, lane, pval, pbase, poff,
+                                                   pmask, qi, qi_ld, b, nbuf, dc);
+  }
+}
+
+// Frames of any sample type to planar records (the fallback of the frame entry points and the
+// gather of the seed buffers): y[c·ys + t] = x[t·fs + c], t < nframe. A tile of 256 frames goes
+// through LDS, read as the frames lie and written as one 256-sample run per channel.
+// Dynamic LDS: 256·nch·sizeof(XT) bytes.
+template <typename XT>
+__global__ __launch_bounds__(256) void deinterleave_frames_kernel(const XT* __restrict__ x, int nch, int64_t fs,
+                                                                  int64_t nframe, XT* __restrict__ y, int64_t ys) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds_tile[];
+  XT* tile = reinterpret_cast<XT*>(lds_tile);
+  const int tid = threadIdx.x;
+  for (int64_t t0 = (int64_t)blockIdx.x * 256; t0 < nframe; t0 += (int64_t)gridDim.x * 256) {
+    const int nf = nframe - t0 < 256 ? (int)(nframe - t0) : 256;
+    for (int i = tid; i < nf * nch; i += 256) {
+      const int f = i / nch;
+      tile[i] = x[(t0 + f) * fs + (i - f * nch)];
+    }
+    __syncthreads();
+    if (tid < nf)
+      for (int c = 0; c < nch; ++c) y[c * ys + t0 + tid] = tile[tid * nch + c];
+    __syncthreads();
+  }
+}
+
 // Many harmonics (the bin kernel's LDS basis, 2·ndata·L doubles, no longer fits beside the
 // bins: ndata > 16 at L = 200). The fold is the bin kernel's (bins in LDS, flat 1-KB wave
 // loads); each wave folds KSEG consecutive segments into KSEG bin sets and then contracts

@@ -95,6 +95,7 @@ struct Tuning {
   int demod_wide_rmax = 2000;  // segments shorter than this go through demod_wide_kernel too
   int demod_wide_half = 1;  // demod_wide_kernel: half-wave contraction at 2·ndata + 1 <= 32 (0: off, A/B)
   int demod_i16_int = 1;    // int16 records: the bin kernels fold by integer accumulation (0: the LDS-bin fold, A/B)
+  int demod_frames = 1;     // int16 frames of 2 / 4 / 8 channels: demod_frames_kernel (0: de-interleave first, A/B)
   int demod_wide_dbg = 0;   // diagnostics: demod_wide_kernel without its contraction (1) / stores (2)
   int demod_wide_k = 0;     // demod_wide_kernel segments per wave (KSEG): 0 = 8; 2 / 4 / 8 (A/B)
   int ekf_row = 1;       // EKF: ekf_row_kernel (4 channels per wave) up to ekf_row x 4 x 4 x CUs channels
@@ -928,6 +929,103 @@ int demod_device(const XT* x, int64_t nseg, int64_t stride, int R, int ndata, do
   return DFMI_OK;
 }
 
+// ---- frame-interleaved records: x[(b·R + t)·frame_stride + c] (include/dfmi.h) ----
+constexpr int kFramesMaxCh = 32;  // deinterleave_frames_kernel's tile: 256 frames x nch samples in LDS (64 KB of doubles)
+
+// Whether demod_frames_kernel folds these frames. What it needs: int16 frames of 2, 4 or 8
+// channels with no padding; the bin kernels' geometry at two period slots (even 128 <= L <= 256,
+// at most 16 harmonics, the basis and four bin sets within the LDS budget — the planar call's
+// own condition for the integer bin fold) and its overflow guard; and aligned wide loads: the two
+// frames of a lane are 4·nch bytes, loaded as one dwordx2 (8-B aligned) or as dwordx4 (16-B
+// aligned), at byte offset 2·nch·(b·R + k·L + p) with L and p even: so x aligned to
+// min(4·nch, 16) bytes and R even. And the planar call must take the bin kernel too (not
+// demod_wide_kernel ahead of it, whose QI differ in the last bits), since its bits are the contract.
+template <typename XT>
+bool frames_native(const XT* x, int nch, int64_t fs, int R, int L, int ndata) {
+  if (!std::is_same<XT, int16_t>::value || !t_tune.demod_frames) return false;
+  if ((nch != 2 && nch != 4 && nch != 8) || fs != nch) return false;
+  if (((uintptr_t)x & (size_t)((4 * nch < 16 ? 4 * nch : 16) - 1)) || (R & 1)) return false;
+  if (L <= 0 || L > 256 || ndata > 16 || !bins_applicable(true, L, ndata, t_ds->lds_per_block)) return false;
+  if (wide_first(ndata, R) && wide_geometry(true, L, ndata)) return false;
+  return i16_int_fold<int16_t>(R, L);
+}
+
+// Loads in flight / cycles prefetched per channel count: 12 / 16 / 16 dwords per lane in flight
+// (the planar integer fold: 10), 8 / 8 / 16 of the next buffer prefetched across the contractions.
+template <int NCH, bool ROWS>
+int launch_frames_t(const int16_t* x, int64_t nbuf, int R, int L, int ndata, const double* tab, double* qi,
+                    int64_t qi_ld, double* dc, hipStream_t st) {
+  constexpr int LOADS = NCH == 2 ? 6 : NCH == 4 ? 4 : 2, PFN = NCH == 2 ? 2 : 1;
+  auto kern = dfmi::demod_frames_kernel<NCH, 2, LOADS, ROWS, PFN>;
+  const size_t lds = (size_t)2 * ndata * L * sizeof(double);
+  int per_cu = 0;
+  if (int orc = occupancy(kern, dfmi::kBlockThreads, lds, &per_cu)) return orc;
+  if (per_cu < 1) per_cu = 1;
+  const int64_t grid = bins_grid(t_ds->n_cu, per_cu, nbuf);
+  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(dfmi::kBlockThreads), lds, st, x, nbuf, R, L, ndata, tab, qi,
+                     qi_ld, dc);
+  HIPCHK(hipGetLastError());
+  g_last_demod = "demod_frames_kernel<" + std::to_string(NCH) + ",2," + std::to_string(LOADS) + (ROWS ? ",rows," : ",") +
+                 std::to_string(PFN) + "> [i16 int, " + std::to_string(NCH) + " ch]";
+  return DFMI_OK;
+}
+
+// frames_native() holds. Column c·nbuf + b of qi (rows: row c·nbuf + b, dc inside).
+int launch_frames(const int16_t* x, int nch, int64_t nbuf, int R, int L, int ndata, double w0, double* qi,
+                  int64_t qi_ld, double* dc, hipStream_t st, bool rows) {
+  const double* tab = nullptr;
+  if (int rc = basis_table(L, ndata, w0, &tab)) return rc;
+#define DFMI_FRAMES(N_)                                                                    \
+  return rows ? launch_frames_t<N_, true>(x, nbuf, R, L, ndata, tab, qi, qi_ld, dc, st)    \
+              : launch_frames_t<N_, false>(x, nbuf, R, L, ndata, tab, qi, qi_ld, dc, st)
+  if (nch == 2) DFMI_FRAMES(2);
+  if (nch == 4) DFMI_FRAMES(4);
+  DFMI_FRAMES(8);
+#undef DFMI_FRAMES
+}
+
+// y[c·ys + t] = x[t·fs + c] for t < nframe (deinterleave_frames_kernel).
+template <typename XT>
+int deinterleave(const XT* x, int nch, int64_t fs, int64_t nframe, XT* y, int64_t ys, hipStream_t st) {
+  int64_t grid = (nframe + 255) / 256;
+  if (grid > (int64_t)t_ds->n_cu * 16) grid = (int64_t)t_ds->n_cu * 16;
+  hipLaunchKernelGGL(dfmi::deinterleave_frames_kernel<XT>, dim3((unsigned)grid), dim3(256),
+                     (size_t)256 * nch * sizeof(XT), st, x, nch, fs, nframe, y, ys);
+  HIPCHK(hipGetLastError());
+  return DFMI_OK;
+}
+
+// The planar copy of the frames' nch records of nbuf·R samples ("frames_planar", in XT).
+template <typename XT>
+int frames_planar(const XT* x, int nch, int64_t fs, int64_t nbuf, int R, hipStream_t st, const XT** out) {
+  void* w = nullptr;
+  const int64_t n = nbuf * (int64_t)R;
+  if (int rc = workspace("frames_planar", (size_t)nch * n * sizeof(XT), &w)) return rc;
+  *out = (const XT*)w;
+  return deinterleave(x, nch, fs, n, (XT*)w, n, st);
+}
+
+template <typename XT>
+int demod_frames_device(const XT* x, int nch, int64_t fs, int64_t nbuf, int R, int ndata, double w0, int period,
+                        double* qi, double* dc, hipStream_t st) {
+  int L = period;
+  if (L == 0) L = detect_period_impl(w0, R, ndata);
+  if (frames_native(x, nch, fs, R, L, ndata))
+    return launch_frames((const int16_t*)x, nch, nbuf, R, L, ndata, w0, qi, nch * nbuf, dc, st, false);
+  const XT* xp = nullptr;
+  int rc = frames_planar(x, nch, fs, nbuf, R, st, &xp);
+  if (rc) return rc;
+  if ((rc = demod_device(xp, nch * nbuf, R, R, ndata, w0, period, qi, nch * nbuf, dc, st))) return rc;
+  g_last_demod += " [frames copied]";
+  return DFMI_OK;
+}
+
+// The record pipeline's demodulation input when the records arrive as frames (nls_record_device).
+struct FramesIn {
+  const int16_t* x;
+  int nch;
+};
+
 // LM variant selection, stated once for the one-lane kernels (lm_kernel) and the lambda ladder
 // (lm_ladder): the register path (ndata <= 16; the exact-ndata variant with QI in registers for
 // the reference default ndata = 10) or the general path (any ndata, or lm_general = 1).
@@ -1180,7 +1278,10 @@ template <typename XT>
 int nls_record_device(const XT* x, int64_t nrec, int64_t rec_stride, int64_t nbuf, int R, int ndata,
                       double w0, int period, const double* init_guess_host, int parallel, int64_t nchunk,
                       const dfmi_lm_config& cfg, const dfmi::LMConst& c, double* out, int32_t* fitok,
-                      hipStream_t st) {
+                      hipStream_t st, const FramesIn* fr = nullptr) {
+  // fr (frames_native() holds): the nrec = fr->nch records arrive as frames at fr->x and x is
+  // the planar copy of their seed buffers (rec_stride R); the seed runs on x beside
+  // demod_frames_kernel on the frames, everything else is the two-kernel sequence below
   const int64_t nseg = nrec * nbuf;
   if (nseg == 0) return DFMI_OK;
   DeviceState& ds = *t_ds;
@@ -1215,7 +1316,7 @@ int nls_record_device(const XT* x, int64_t nrec, int64_t rec_stride, int64_t nbu
   const bool rows = parallel && (nbuf <= 1 || nchunk >= nbuf - 1) && even_recs && !wide &&
                     rows_supported(x, R, R, ndata, w0, period);
   const int64_t qs = rows ? dfmi_row_stride(ndata) : 0;
-  if (parallel && rows && (nrec == 1 || rec_stride == nbuf * (int64_t)R) && nbuf > 1) {
+  if (!fr && parallel && rows && (nrec == 1 || rec_stride == nbuf * (int64_t)R) && nbuf > 1) {
     // ONE launch: the seeds (buffer 0 of every record) + the bulk demodulation; the LM
     // follows in stream order
     const double* tab = nullptr;
@@ -1256,7 +1357,9 @@ int nls_record_device(const XT* x, int64_t nrec, int64_t rec_stride, int64_t nbu
     if (rc) return rc;
     qi = (double*)w;
   }
-  if (rec_stride == nbuf * (int64_t)R || nrec == 1) {
+  if (fr) {
+    rc = launch_frames(fr->x, fr->nch, nbuf, R, L, ndata, w0, qi, rows ? qs : nseg, dc, st, rows);
+  } else if (rec_stride == nbuf * (int64_t)R || nrec == 1) {
     rc = rows ? demod_device(x, nseg, R, R, ndata, w0, period, qi, qs, nullptr, st, true)
               : demod_device(x, nseg, R, R, ndata, w0, period, qi, nseg, dc, st);
   } else {
@@ -1311,6 +1414,7 @@ const std::map<std::string, Knob>& knobs() {
       {"lm_split_from", {&Tuning::lm_split_from, {}}},
       {"demod_wide_half", {&Tuning::demod_wide_half, {0, 1}}},
       {"demod_i16_int", {&Tuning::demod_i16_int, {0, 1}}},
+      {"demod_frames", {&Tuning::demod_frames, {0, 1}}},
       {"demod_wide_dbg", {&Tuning::demod_wide_dbg, {0, 1, 2, 3, 4, 5, 6, 7}}},
       {"ekf_row", {&Tuning::ekf_row, {}}},
       {"ekf_rot", {&Tuning::ekf_rot, {0, 1}}},
@@ -1845,6 +1949,87 @@ int nls_record_impl(const XT* x, int64_t nrec, int64_t rec_stride, int64_t nbuf,
   return sg.finish();
 }
 
+// Bodies of dfmi_demod_frames / dfmi_nls_record_frames over the sample type XT.
+int bad_frames(int32_t nch, int64_t fs, int64_t nbuf, int32_t R, int32_t ndata) {
+  if (nch < 1 || nch > kFramesMaxCh) return fail(DFMI_ERR_ARG, "frames: 1 <= nch <= 32");
+  if (fs < nch) return fail(DFMI_ERR_ARG, "frame_stride < nch");
+  if (nbuf < 0 || R <= 0 || ndata <= 0) return fail(DFMI_ERR_ARG, "bad frame geometry");
+  return DFMI_OK;
+}
+
+template <typename XT>
+int demod_frames_impl(const XT* x, int32_t nch, int64_t fs, int64_t nbuf, int32_t R, int32_t ndata, double w0,
+                      int32_t period, double* qi, double* dc, int32_t mem, void* stream) {
+  CallScope cs(stream);
+  int rc = bad_frames(nch, fs, nbuf, R, ndata);
+  if (rc) return rc;
+  if (nbuf > 0 && (!x || !qi || !dc)) return fail(DFMI_ERR_ARG, "null pointer");
+  if ((rc = ensure_init())) return rc;
+  if (nbuf == 0) return DFMI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  Staging sg(mem, st);
+  const int64_t nseg = nch * nbuf;
+  const XT* dx;
+  double *dq, *dd;
+  if ((rc = sg.in("f_x", x, (size_t)((nbuf * R - 1) * fs + nch) * sizeof(XT), &dx))) return rc;
+  if ((rc = sg.out("d_qi", qi, (size_t)2 * ndata * nseg * 8, &dq))) return rc;
+  if ((rc = sg.out("d_dc", dc, (size_t)nseg * 8, &dd))) return rc;
+  if ((rc = demod_frames_device(dx, nch, fs, nbuf, R, ndata, w0, period, dq, dd, st))) return rc;
+  return sg.finish();
+}
+
+template <typename XT>
+int nls_record_frames_impl(const XT* x, int32_t nch, int64_t fs, int64_t nbuf, int32_t R, int32_t ndata, double w0,
+                           int32_t period, const double* init_guess, int32_t parallel, int64_t nchunk,
+                           const dfmi_lm_config* cfg, double* out, int32_t* fitok, int32_t mem, void* stream) {
+  CallScope cs(stream);
+  int rc = bad_frames(nch, fs, nbuf, R, ndata);
+  if (rc) return rc;
+  if (nbuf > 0 && (!x || !init_guess || !out || !fitok)) return fail(DFMI_ERR_ARG, "null pointer");
+  dfmi_lm_config dcfg;
+  if (!cfg) {
+    dfmi_lm_config_default(&dcfg);
+    cfg = &dcfg;
+  }
+  dfmi::LMConst c;
+  if ((rc = to_lmconst(cfg, &c))) return rc;
+  if ((rc = ensure_init())) return rc;
+  if (nbuf == 0) return DFMI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  Staging sg(mem, st);
+  const int64_t nseg = nch * nbuf;
+  const XT* dx;
+  double* dout;
+  int32_t* dst;
+  if ((rc = sg.in("f_x", x, (size_t)((nbuf * R - 1) * fs + nch) * sizeof(XT), &dx))) return rc;
+  if ((rc = sg.out("n_out", out, (size_t)6 * nseg * 8, &dout))) return rc;
+  if ((rc = sg.out("n_status", fitok, (size_t)nseg * 4, &dst))) return rc;
+  int L = period;
+  if (L == 0) L = detect_period_impl(w0, R, ndata);
+  if (frames_native(dx, nch, fs, R, L, ndata)) {
+    // parallel: the seed buffers (buffer 0 of every channel) as planar records for the seed
+    // kernels. Sequential: there is no seed step and nls_record_device reads nothing through x
+    // (only its pair alignment, which the frames' own base has), so no staging is made
+    const int16_t* seed = (const int16_t*)dx;
+    if (parallel) {
+      void* sw = nullptr;
+      if ((rc = workspace("frames_seed", (size_t)nch * R * sizeof(int16_t), &sw))) return rc;
+      if ((rc = deinterleave((const int16_t*)dx, nch, fs, (int64_t)R, (int16_t*)sw, (int64_t)R, st))) return rc;
+      seed = (const int16_t*)sw;
+    }
+    const FramesIn fr{(const int16_t*)dx, nch};
+    rc = nls_record_device(seed, nch, R, nbuf, R, ndata, w0, period, init_guess, parallel, nchunk, *cfg, c, dout, dst,
+                           st, &fr);
+  } else {
+    const XT* xp = nullptr;
+    if ((rc = frames_planar(dx, nch, fs, nbuf, R, st, &xp))) return rc;
+    rc = nls_record_device(xp, nch, nbuf * (int64_t)R, nbuf, R, ndata, w0, period, init_guess, parallel, nchunk, *cfg,
+                           c, dout, dst, st);
+    g_last_demod += " [frames copied]";
+  }
+  if (rc) return rc;
+  return sg.finish();
+}
 
 int bad_xtype(int32_t xtype) {
   return xtype != DFMI_F64 && xtype != DFMI_F32 && xtype != DFMI_I16;
@@ -2037,6 +2222,31 @@ int dfmi_nls_record_typed(const void* x, int32_t xtype, int64_t nrec, int64_t re
     return nls_record_impl<int16_t>((const int16_t*)x, nrec, rec_stride, nbuf, R, ndata, w0, period, init_guess,
                                     parallel, nchunk, cfg, out, fitok, mem, stream);
   return nls_record_impl<float>((const float*)x, nrec, rec_stride, nbuf, R, ndata, w0, period, init_guess, parallel,
+                                nchunk, cfg, out, fitok, mem, stream);
+}
+
+int dfmi_demod_frames(const void* x, int32_t xtype, int32_t nch, int64_t frame_stride, int64_t nbuf, int32_t R,
+                      int32_t ndata, double w0, int32_t period, double* qi, double* dc, int32_t mem, void* stream) {
+  if (bad_xtype(xtype)) return fail(DFMI_ERR_ARG, "unknown sample type");
+  if (xtype == DFMI_F64)
+    return demod_frames_impl((const double*)x, nch, frame_stride, nbuf, R, ndata, w0, period, qi, dc, mem, stream);
+  if (xtype == DFMI_I16)
+    return demod_frames_impl((const int16_t*)x, nch, frame_stride, nbuf, R, ndata, w0, period, qi, dc, mem, stream);
+  return demod_frames_impl((const float*)x, nch, frame_stride, nbuf, R, ndata, w0, period, qi, dc, mem, stream);
+}
+
+int dfmi_nls_record_frames(const void* x, int32_t xtype, int32_t nch, int64_t frame_stride, int64_t nbuf, int32_t R,
+                           int32_t ndata, double w0, int32_t period, const double* init_guess, int32_t parallel,
+                           int64_t nchunk, const dfmi_lm_config* cfg, double* out, int32_t* fitok, int32_t mem,
+                           void* stream) {
+  if (bad_xtype(xtype)) return fail(DFMI_ERR_ARG, "unknown sample type");
+  if (xtype == DFMI_F64)
+    return nls_record_frames_impl((const double*)x, nch, frame_stride, nbuf, R, ndata, w0, period, init_guess, parallel,
+                                  nchunk, cfg, out, fitok, mem, stream);
+  if (xtype == DFMI_I16)
+    return nls_record_frames_impl((const int16_t*)x, nch, frame_stride, nbuf, R, ndata, w0, period, init_guess,
+                                  parallel, nchunk, cfg, out, fitok, mem, stream);
+  return nls_record_frames_impl((const float*)x, nch, frame_stride, nbuf, R, ndata, w0, period, init_guess, parallel,
                                 nchunk, cfg, out, fitok, mem, stream);
 }
 

@@ -197,6 +197,83 @@ def nls_records(records, f_samp, f_mod, R, nbuf, ndata=10, init_guess=(1.6, 6.0,
     return out, ok
 
 
+def nls_frames(frames, f_samp, f_mod, R, nbuf, ndata=10, init_guess=(1.6, 6.0, 0.0, 0.0), parallel=True,
+               n_cores=None, errors=False):
+    """nls_records on the nch records that frame-interleaved samples hold, with no transposed
+    copy: frames is a 2-D (N >= nbuf*R, nch) numpy array or CUDA tensor with stride(1) == 1
+    (row t = sample t of every channel, as a digitiser delivers them; stride(0) > nch: padded
+    frames) of float64, float32 or int16. Returns what nls_records returns for the planar records
+    frames[:, c], channel by channel (segment c*nbuf + b), bit for bit. int16 frames of 2, 4 or
+    8 channels are folded as they lie (dfmi_nls_record_frames, include/dfmi.h); anything else
+    is de-interleaved on the device first."""
+    if errors:
+        _check_errors_ndata(ndata)
+    dev = _is_device_tensor(frames)
+    if not dev:
+        frames = _host_samples(frames)
+    if frames.ndim != 2:
+        raise ValueError("frames must be 2-D (samples, channels)")
+    n, nch = int(frames.shape[0]), int(frames.shape[1])
+    s0, s1 = (frames.stride(0), frames.stride(1)) if dev else (k // frames.itemsize for k in frames.strides)
+    if nch > 1 and s1 != 1 or n > 1 and s0 < nch:
+        raise ValueError("frames must have stride(1) == 1 and stride(0) >= nch")
+    if n < nbuf * R:
+        raise ValueError("frames hold fewer than nbuf*R samples per channel")
+    xtype = _xtype(frames.dtype)
+    if xtype is None:
+        raise ValueError("frames must be float64, float32 or int16")
+    lib = _lib.load()
+    w0 = w0_of(f_mod, f_samp)
+    g = np.asarray(init_guess, dtype=np.float64)
+    g = np.ascontiguousarray(np.broadcast_to(g, (nch, 4)) if g.ndim == 1 else g)
+    nchunk = (nbuf - 1) if n_cores is None else max(1, min(int(n_cores), nbuf))
+    cfg = _fit.lm_config()
+    nseg = nch * nbuf
+    fs = int(s0) if n > 1 else nch
+    if dev:
+        import torch
+        out = torch.empty((7, nseg), dtype=torch.float64, device=frames.device)[:6]
+        out._dfmi_block = True  # as nls_records: frame_from may use row 6
+        ok = torch.empty(nseg, dtype=torch.int32, device=frames.device)
+        mem, stream, ctx = _lib.DFMI_MEM_DEVICE, _torch_stream(frames.device), _on_device(frames)
+    else:
+        import contextlib
+        out = np.empty((6, nseg))
+        ok = np.empty(nseg, dtype=np.int32)
+        mem, stream, ctx = _lib.DFMI_MEM_HOST, None, contextlib.nullcontext()
+    with ctx:
+        rc = lib.dfmi_nls_record_frames(_lib.ptr(frames), xtype, nch, fs, nbuf, R, ndata, w0, 0, _lib.ptr(g),
+                                        1 if parallel else 0, max(nchunk, 1), cfg, _lib.ptr(out), _lib.ptr(ok), mem,
+                                        stream)
+        _lib.check(rc, "dfmi_nls_record_frames")
+        if errors:
+            return out, ok, _segment_errors(lib, out, nseg, ndata, mem, stream)
+    return out, ok
+
+
+def frames_of(xs):
+    """The 2-D (N, nch) frames view whose columns 0..nch-1, in order, are the 1-D arrays or CUDA
+    tensors xs (same storage, same row stride, consecutive addresses: the column views of one
+    frames block, DeepFitFramework.load_frames), or None for any other set of records."""
+    x0 = xs[0]
+    dev = _is_device_tensor(x0)
+    if len(xs) < 2 or not (dev or isinstance(x0, np.ndarray)) or x0.ndim != 1 or _xtype(x0.dtype) is None:
+        return None
+    item = x0.element_size() if dev else x0.itemsize
+    stride = (lambda x: x.stride(0)) if dev else (lambda x: x.strides[0] // item)
+    store = (lambda x: x.untyped_storage().data_ptr()) if dev else (lambda x: 0)
+    for c, x in enumerate(xs):
+        if (type(x) is not type(x0) or x.dtype != x0.dtype or x.shape != x0.shape or stride(x) != stride(x0)
+                or store(x) != store(x0) or _lib.ptr(x) != _lib.ptr(x0) + c * item):
+            return None
+    n, s = int(x0.shape[0]), int(stride(x0))
+    if s < len(xs):
+        return None
+    if dev:
+        return x0.as_strided((n, len(xs)), (s, 1))
+    return np.lib.stride_tricks.as_strided(x0, (n, len(xs)), (s * item, item), writeable=False)
+
+
 def nls_record_devices(x, f_samp, f_mod, R, nbuf, devices, ndata=10, init_guess=(1.6, 6.0, 0.0, 0.0),
                        errors=False):
     """One record's _fit_parallel with chunk size 1 (fitters.py:395-428: buffer 0 fitted from
@@ -409,19 +486,26 @@ class StandardNLSFitter(BaseFitter):
             raise ValueError("devices= applies to parallel=True without n_cores (chunk size 1); "
                              f"got parallel={parallel}, n_cores={kwargs.get('n_cores')}")
         mark("fitter_args")
+        fit_records = nls_records
+        if devices is None:
+            if _is_device_tensor(x) and N > 1 and x.stride(0) != 1:
+                # a column of a frames block (load_frames): a one-channel frames call, no copy here
+                one, fit_records = x[:, None], nls_frames
+            else:
+                one = x.reshape(1, N)
         if errors:
             g = (init_a, init_m, 0.0, init_psi)
             if devices is not None:
                 res = nls_record_devices(x, main_raw.f_samp, main_raw.f_mod, R, nbuf, devices, ndata, g, errors=True)
             else:
-                res = nls_records(x.reshape(1, N), main_raw.f_samp, main_raw.f_mod, R, nbuf, ndata, g,
+                res = fit_records(one, main_raw.f_samp, main_raw.f_mod, R, nbuf, ndata, g,
                                   parallel=parallel, n_cores=kwargs.get("n_cores") if parallel else None, errors=True)
             return frame_with_errors(*res)
         if devices is not None:
             cols, ok = nls_record_devices(x, main_raw.f_samp, main_raw.f_mod, R, nbuf, devices, ndata,
                                           (init_a, init_m, 0.0, init_psi))
             return frame_from(cols, ok)
-        cols, ok = nls_records(x.reshape(1, N), main_raw.f_samp, main_raw.f_mod, R, nbuf, ndata,
+        cols, ok = fit_records(one, main_raw.f_samp, main_raw.f_mod, R, nbuf, ndata,
                                (init_a, init_m, 0.0, init_psi), parallel=parallel,
                                n_cores=kwargs.get("n_cores") if parallel else None)
         return frame_from(cols, ok, tau_divisor(main_raw))

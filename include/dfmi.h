@@ -179,6 +179,34 @@ int dfmi_nls_record_typed(const void* x, int32_t xtype, int64_t nrec, int64_t re
                           int64_t nchunk, const dfmi_lm_config* cfg, double* out, int32_t* fitok, int32_t mem,
                           void* stream);
 
+/* Frame-interleaved records (what a digitiser delivers: sample t of every channel side by
+ * side): x[(b * R + t) * frame_stride + c] for channel c < nch, buffer b < nbuf, of type xtype;
+ * frame_stride >= nch in ELEMENTS (> nch: padded frames), 1 <= nch <= 32. dfmi_demod_frames and
+ * dfmi_nls_record_frames are dfmi_demod_typed and dfmi_nls_record_typed on the nrec = nch
+ * records the frames de-interleave to, with the outputs indexed as those calls index them:
+ * qi[k * (nch * nbuf) + c * nbuf + b], dc[c * nbuf + b], out[col * (nch * nbuf) + c * nbuf + b],
+ * fitok[c * nbuf + b], init_guess[c * 4 + i]; bit for bit what the planar call gives on the
+ * de-interleaved copy. DFMI_ERR_ARG: nch < 1 (or > 32), frame_stride < nch, an unknown xtype.
+ * int16 frames of 2, 4 or 8 channels are folded as they lie, with no copy (demod_frames_kernel:
+ * one wave per buffer, one set of int32 bins per channel, one or two 8 / 16-byte loads per lane
+ * for the two frames it owns; reported as "demod_frames_kernel<...> [i16 int, N ch]") when
+ *   - frame_stride == nch and R is even,
+ *   - x is aligned to min(4 * nch, 16) bytes (the wide loads' alignment: 8 B at 2 channels,
+ *     16 B at 4 and 8),
+ *   - the planar call would run the integer bin fold: an even period 128 <= L <= 256, at most
+ *     16 harmonics, ceil(R / L) <= 65535, and the many-harmonic kernel not going ahead of the
+ *     bin kernel (ndata < 13 and R >= 2000 at the default tuning).
+ * Everything else (float / double frames, other channel counts, padded frames, an unaligned
+ * view, other geometry, the tuning key "demod_frames" = 0) is first de-interleaved on the
+ * device into a workspace of the frames' own sample type and then takes the planar typed path:
+ * its string followed by " [frames copied]". DFMI_MEM_HOST stages the frames in their own type. */
+int dfmi_demod_frames(const void* x, int32_t xtype, int32_t nch, int64_t frame_stride, int64_t nbuf, int32_t R,
+                      int32_t ndata, double w0, int32_t period, double* qi, double* dc, int32_t mem, void* stream);
+int dfmi_nls_record_frames(const void* x, int32_t xtype, int32_t nch, int64_t frame_stride, int64_t nbuf, int32_t R,
+                           int32_t ndata, double w0, int32_t period, const double* init_guess, int32_t parallel,
+                           int64_t nchunk, const dfmi_lm_config* cfg, double* out, int32_t* fitok,
+                           int32_t mem, void* stream);
+
 /* Per-sample EKF (fitters.py:214-320) over nrec independent channels, each a serial
  * chain over its samples: up to 16 x CUs channels one 16-lane DPP row per channel (4 per
  * wave; ekf_rot_kernel with sin / cos by rotation between anchors when R % 4 == 0, else
