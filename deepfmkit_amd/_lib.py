@@ -33,7 +33,8 @@ SYMBOLS = ("dfmi_lm_config_default", "dfmi_demod", "dfmi_lm", "dfmi_nls_record",
            "dfmi_release_workspaces", "dfmi_step_timing", "dfmi_step_timing_read", "dfmi_ekf_pit_passes",
            "dfmi_ekf_pit_trace", "dfmi_demod_typed", "dfmi_demod_rows_typed", "dfmi_nls_record_typed",
            "dfmi_fisher", "dfmi_lpsd_plan", "dfmi_lpsd", "dfmi_plnoise_design", "dfmi_plnoise",
-           "dfmi_synth_asd_coloured", "dfmi_lcsd", "dfmi_demod_frames", "dfmi_nls_record_frames")
+           "dfmi_synth_asd_coloured", "dfmi_lcsd", "dfmi_demod_frames", "dfmi_nls_record_frames",
+           "dfmi_demod_hop", "dfmi_nls_record_hop")
 
 
 class DFMIError(RuntimeError):
@@ -217,6 +218,11 @@ def load():
         lib.dfmi_demod_frames.restype = ctypes.c_int
         lib.dfmi_nls_record_frames.argtypes = [P, i32, i32, i64, i64] + lib.dfmi_nls_record.argtypes[4:]
         lib.dfmi_nls_record_frames.restype = ctypes.c_int
+        # overlapped segments: (x, xtype, nrec, rec_stride, nseg, R, hop, ...the planar arguments after R)
+        lib.dfmi_demod_hop.argtypes = [P, i32, i64, i64, i64, i32, i32] + lib.dfmi_demod.argtypes[4:]
+        lib.dfmi_demod_hop.restype = ctypes.c_int
+        lib.dfmi_nls_record_hop.argtypes = [P, i32, i64, i64, i64, i32, i32] + lib.dfmi_nls_record.argtypes[5:]
+        lib.dfmi_nls_record_hop.restype = ctypes.c_int
         lib.dfmi_ekf.argtypes = [P, i64, i64, i64, P, P, P, P, dbl, dbl, i32, i64, P, i32, P]
         lib.dfmi_ekf.restype = ctypes.c_int
         lib.dfmi_ekf_fit.argtypes = [P, i64, i64, i64, P, P, P, P, dbl, dbl, i32, i64, P, i32, P]

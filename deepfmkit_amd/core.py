@@ -269,7 +269,14 @@ class DeepFitFramework:
         errors=True (method 'nls' only): the frame also carries amp_err, m_err, phi_err, psi_err
         (the standard errors at each buffer's fitted parameters, StandardNLSFitter.fit) and
         tau_err = m_err / (2 pi df) (zeros without a simulation); the DeepFitObject gets
-        attributes of the same names. Without it the frame and the object are unchanged."""
+        attributes of the same names. Without it the frame and the object are unchanged.
+
+        hop=k (samples, k < R; method 'nls' only): a sliding-window readout, one point per k
+        samples, each fitted to the R samples that start there. The fit object then has nbuf =
+        (n_samples - R)//k + 1 points, fs = f_samp/k and its time axis on that rate, R unchanged
+        and the new attribute hop; phi_sim_downsamp is the R-sample mean at each hop. Overlapped
+        points share samples: neighbouring points are correlated (a spectrum of the series is
+        that of an R-sample moving average sampled at f_samp/k)."""
         _fitters.mark("fit")
         fitter_map = _fitters.FITTER_MAP
         if method not in fitter_map:
@@ -277,6 +284,9 @@ class DeepFitFramework:
             return
         if kwargs.get("errors") and method != "nls":
             raise ValueError(f"errors=True is available for method 'nls' only, got '{method}'")
+        hop = kwargs.get("hop")
+        if hop is not None and method != "nls":
+            raise ValueError(f"hop= is available for method 'nls' only, got '{method}'")
         if main_label not in self.raws:
             log.error(f"Invalid raw data label: '{main_label}' !!")
             return
@@ -285,8 +295,18 @@ class DeepFitFramework:
             fit_label = f"{main_label}_{method}"
         n = self._n_cycles(raw, main_label, kwargs)
         R, fs, nbuf = self.fit_init(main_label, n)
+        if hop is not None and int(hop) != R:
+            hop = int(hop)
+            fs, nbuf = raw.f_samp / hop, max((raw.n_samples() - R) // hop + 1, 0)
+        else:
+            hop = None
         if getattr(raw, "phi_sim", None) is not None and len(raw.phi_sim) > 0:
-            raw.phi_sim_downsamp = vectorized_downsample(raw.phi_sim, R)
+            if hop is None:
+                raw.phi_sim_downsamp = vectorized_downsample(raw.phi_sim, R)
+            else:  # the R-sample mean at each hop
+                c = np.concatenate(([0.0], np.cumsum(np.asarray(raw.phi_sim, dtype=np.float64))))
+                i = np.arange(nbuf) * hop
+                raw.phi_sim_downsamp = (c[i + R] - c[i]) / R
         fit_config = {"n": n}
         fitter_args = {"main_raw": raw}
         if "wdfmi" in method:  # core.py:486-490 (hwdfmi included)
@@ -303,7 +323,9 @@ class DeepFitFramework:
         # the package's own NLS fitter returns frame_from's frame untouched: its column arrays
         # can be used as they are (any other fitter's frame is read through pandas)
         known = _fitters.frame_arrays(df) if type(fitter) is _fitters.StandardNLSFitter else None
-        return self._finish(fit_label, main_label, raw, method, df, n, R, fs, nbuf, known)
+        fit = self._finish(fit_label, main_label, raw, method, df, n, R, fs, nbuf, known)
+        fit.hop = R if hop is None else hop
+        return fit
 
     def _finish(self, fit_label, main_label, raw, method, df, n, R, fs, nbuf, known=None):
         arrays, with_tau = known if known is not None else (None, None)

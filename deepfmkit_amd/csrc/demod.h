@@ -962,6 +962,179 @@ __global__ __launch_bounds__(kBlockThreads) void demod_frames_kernel(
   }
 }
 
+// Overlapped segments: segment s of a record is x[s·hop + t], t < R = V·hop, so consecutive
+// segments share V - 1 HOP BLOCKS of hop samples. With hop a whole number of basis periods
+// (hop % L == 0) a segment's phase bins are the sum of its V blocks' bins, and a block's bins
+// serve the V segments that contain it: every sample is loaded and added once, and only the
+// small contraction (fold_finish) repeats per output point.
+// Work unit: a SPAN of up to G consecutive segments of one record = G + V - 1 contiguous hop
+// blocks, taken by one wave (persistent grid-stride over record x span, four-wave workgroups
+// sharing one LDS copy of the basis); the V - 1 halo blocks are what a span reads beyond its
+// share: HBM traffic (G + V - 1) / G of the record.
+// Block fold: fold_segment's lane mapping (lane l, slot j owns bins 2·(l + 64·j) + e), one
+// non-temporal pair load per lane, slot and cycle, LOADS pairs in flight; lanes whose pair lies
+// past L re-read their slot-0 pair and drop it (iacc_lanes). Bins are int32 for int16 counts
+// (exact, as bins_segment_iacc) and double otherwise. The first PFN cycles of the next block are
+// in flight while a segment is contracted.
+// Ring: the last V blocks' bins stay in registers, V x 4 values per lane. The block loop is
+// unrolled by V so the ring slot is a compile-time index (a dynamic one would send the ring to
+// scratch); no LDS for the ring and no barrier after the table staging.
+// Segment finish: the ring summed OLDEST BLOCK FIRST (each block's bins summed in ascending t
+// from zero): a fixed order, so a segment's bits do not depend on how the record was cut into
+// spans; converted to double once (int path: the planar integer fold's bins exactly, hence its
+// bits) and handed to the unchanged fold_finish with column r·nseg + s.
+// Preconditions (host-checked): L even, 128 <= L <= 256, hop % L == 0, x / rec_stride aligned to
+// sample pairs, the basis in LDS; int16: ceil(V·hop / L) <= 65535.
+template <typename XT>
+struct HopT {  // double / float: the pair as loaded, widened when it is added
+  using S = XT;
+  using Bin = double;
+  typedef XT Raw __attribute__((ext_vector_type(2)));
+  __device__ static __forceinline__ Raw load(const S* p) {
+    return __builtin_nontemporal_load(reinterpret_cast<const Raw*>(p));  // global_load_dwordx4 / x2 ... nt
+  }
+  __device__ static __forceinline__ void add(Bin (&y)[2], Raw v, bool ok) {
+    y[0] += ok ? (double)v.x : 0.0;
+    y[1] += ok ? (double)v.y : 0.0;
+  }
+};
+template <>
+struct HopT<I16Int> {
+  using S = int16_t;
+  using Bin = int32_t;
+  using Raw = int32_t;
+  __device__ static __forceinline__ Raw load(const S* p) { return iacc_load(p); }
+  __device__ static __forceinline__ void add(Bin (&y)[2], Raw w, bool ok) {
+    w = ok ? w : 0;
+    y[0] += (int32_t)(int16_t)w;  // sample 2l: the low half
+    y[1] += w >> 16;              // sample 2l + 1: the high half, sign-extended
+  }
+};
+
+// One hop block (cpb cycles of L samples at xb) folded into the lane's bins yb, from zero, in
+// ascending t. pf: the block's first npf cycles, already loaded; xn (or null): the next block,
+// whose first npf cycles are issued into pf once this block's own loads are.
+template <typename XT, int MAXSLOT, int UNR, int PFN>
+__device__ __forceinline__ void hop_block(const typename HopT<XT>::S* __restrict__ xb, int cpb, int npf, int L,
+                                          const bool (&pval)[MAXSLOT], const int (&poff)[MAXSLOT],
+                                          typename HopT<XT>::Bin (&yb)[MAXSLOT][2],
+                                          typename HopT<XT>::Raw (&pf)[PFN][MAXSLOT],
+                                          const typename HopT<XT>::S* __restrict__ xn) {
+  using H = HopT<XT>;
+#pragma unroll
+  for (int j = 0; j < MAXSLOT; ++j) yb[j][0] = yb[j][1] = 0;
+#pragma unroll
+  for (int u = 0; u < PFN; ++u)
+    if (u < npf) {  // wave-uniform
+#pragma unroll
+      for (int j = 0; j < MAXSLOT; ++j) H::add(yb[j], pf[u][j], pval[j]);
+    }
+  int k = npf;
+  for (; k + UNR <= cpb; k += UNR) {
+    typename H::Raw v[UNR][MAXSLOT];
+#pragma unroll
+    for (int u = 0; u < UNR; ++u)
+#pragma unroll
+      for (int j = 0; j < MAXSLOT; ++j) v[u][j] = H::load(xb + (k + u) * L + poff[j]);
+#pragma unroll
+    for (int u = 0; u < UNR; ++u)
+#pragma unroll
+      for (int j = 0; j < MAXSLOT; ++j) H::add(yb[j], v[u][j], pval[j]);
+  }
+  {
+    // the remaining (< UNR) cycles and the next block's prefetch as one more load group
+    const int left = cpb - k;  // wave-uniform
+    typename H::Raw v[UNR][MAXSLOT];
+#pragma unroll
+    for (int u = 0; u < UNR; ++u)
+      if (u < left) {
+#pragma unroll
+        for (int j = 0; j < MAXSLOT; ++j) v[u][j] = H::load(xb + (k + u) * L + poff[j]);
+      }
+    if (xn) {
+#pragma unroll
+      for (int u = 0; u < PFN; ++u)
+        if (u < npf) {
+#pragma unroll
+          for (int j = 0; j < MAXSLOT; ++j) pf[u][j] = H::load(xn + u * L + poff[j]);
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < UNR; ++u)
+      if (u < left) {
+#pragma unroll
+        for (int j = 0; j < MAXSLOT; ++j) H::add(yb[j], v[u][j], pval[j]);
+      }
+  }
+}
+
+// G: segments per span (>= 1). Column / row r·nseg + s of qi (fold_finish's two layouts), dc.
+template <typename XT, int V, bool ROWS>
+__global__ __launch_bounds__(kBlockThreads) void demod_hop_kernel(
+    const XT* __restrict__ x, int64_t nrec, int64_t rec_stride, int64_t nseg, int hop, int L, int ndata, int G,
+    const double* __restrict__ tab, double* __restrict__ qi, int64_t qi_ld, double* __restrict__ dc) {
+  static_assert(V == 2 || V == 4 || V == 8, "V");
+  using H = HopT<XT>;
+  constexpr int MS = 2, UNR = 4, PFN = 2;  // 8 pair loads per lane in flight, 4 across a contraction
+  extern __shared__ __attribute__((aligned(16))) double lds_dyn[];
+  stage_table(tab, lds_dyn, 2 * ndata * L, threadIdx.x, kBlockThreads);
+  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int nslot = (L + 127) / 128;
+  int pbase[MS], poff[MS];
+  bool pval[MS];
+#pragma unroll
+  for (int j = 0; j < MS; ++j) {
+    pbase[j] = 2 * (lane + 64 * j);
+    pval[j] = (j < nslot) && (pbase[j] < L);
+    poff[j] = pval[j] ? pbase[j] : pbase[0];
+  }
+  const int R = V * hop;
+  const int cpb = hop / L;
+  const int npf = cpb < PFN ? cpb : PFN;
+  const typename H::S* __restrict__ xs = reinterpret_cast<const typename H::S*>(x);
+  const int64_t nspan = (nseg + G - 1) / G;
+  const int64_t nunit = nrec * nspan;
+  for (int64_t w = (int64_t)blockIdx.x * kWavesPerBlock + wave; w < nunit; w += (int64_t)gridDim.x * kWavesPerBlock) {
+    const int64_t r = w / nspan, s0 = (w - r * nspan) * G;
+    const int nblk = (int)(nseg - s0 < G ? nseg - s0 : G) + V - 1;  // the span's blocks: its segments + the halo
+    const typename H::S* __restrict__ xb = xs + r * rec_stride + s0 * hop;
+    typename H::Bin ring[V][MS][2];
+    typename H::Raw pf[PFN][MS];
+#pragma unroll
+    for (int u = 0; u < PFN; ++u)
+      if (u < npf) {
+#pragma unroll
+        for (int j = 0; j < MS; ++j) pf[u][j] = H::load(xb + u * L + poff[j]);
+      }
+    for (int i0 = 0; i0 < nblk; i0 += V) {
+#pragma unroll
+      for (int u = 0; u < V; ++u) {
+        const int i = i0 + u;  // block i of the span, ring slot u
+        if (i < nblk) {        // wave-uniform
+          hop_block<XT, MS, UNR, PFN>(xb, cpb, npf, L, pval, poff, ring[u], pf, i + 1 < nblk ? xb + hop : nullptr);
+          xb += hop;
+          if (i >= V - 1) {  // segment s0 + i - (V - 1): blocks i - V + 1 .. i, slots u + 1, ..., V - 1, 0, ..., u
+            double y[MS][2];
+#pragma unroll
+            for (int j = 0; j < MS; ++j)
+#pragma unroll
+              for (int e = 0; e < 2; ++e) {
+                typename H::Bin a = ring[(u + 1) % V][j][e];
+#pragma unroll
+                for (int q = 2; q <= V; ++q) a += ring[(u + q) % V][j][e];
+                y[j][e] = (double)a;
+              }
+            fold_finish<2, MS, kHarmBlock, ROWS>(y, pval, pbase, R, L, ndata, lds_dyn, lane, qi, qi_ld,
+                                                 r * nseg + s0 + (i - (V - 1)), dc);
+          }
+        }
+      }
+    }
+  }
+}
+
 // Frames of any sample type to planar records (the fallback of the frame entry points and the
 // gather of the seed buffers): y[c·ys + t] = x[t·fs + c], t < nframe. A tile of 256 frames goes
 // through LDS, read as the frames lie and written as one 256-sample run per channel.

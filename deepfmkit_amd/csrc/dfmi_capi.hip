@@ -96,6 +96,9 @@ struct Tuning {
   int demod_wide_half = 1;  // demod_wide_kernel: half-wave contraction at 2·ndata + 1 <= 32 (0: off, A/B)
   int demod_i16_int = 1;    // int16 records: the bin kernels fold by integer accumulation (0: the LDS-bin fold, A/B)
   int demod_frames = 1;     // int16 frames of 2 / 4 / 8 channels: demod_frames_kernel (0: de-interleave first, A/B)
+  int demod_hop = 1;        // overlapped segments (dfmi_*_hop): demod_hop_kernel where hop_native() holds (0: the planar
+                            // kernels in place at seg_stride = hop, A/B)
+  int demod_hop_span = 0;   // demod_hop_kernel: output segments per span (0: the host's choice, hop_span)
   int demod_wide_dbg = 0;   // diagnostics: demod_wide_kernel without its contraction (1) / stores (2)
   int demod_wide_k = 0;     // demod_wide_kernel segments per wave (KSEG): 0 = 8; 2 / 4 / 8 (A/B)
   int ekf_row = 1;       // EKF: ekf_row_kernel (4 channels per wave) up to ekf_row x 4 x 4 x CUs channels
@@ -1020,6 +1023,107 @@ int demod_frames_device(const XT* x, int nch, int64_t fs, int64_t nbuf, int R, i
   return DFMI_OK;
 }
 
+// ---- overlapped segments: segment s of record r at x[r·rec_stride + s·hop + t], t < R (include/dfmi.h) ----
+
+// Whether demod_hop_kernel folds these segments: hop a whole number of basis periods with V =
+// R / hop of 2, 4 or 8, the bin kernels' geometry at two period slots and at most 16 harmonics (as
+// frames_native), pair-aligned records and hop, and for int16 the integer fold's overflow guard.
+template <typename XT>
+bool hop_native(const XT* x, int64_t nrec, int64_t rec_stride, int R, int hop, int L, int ndata) {
+  if (!t_tune.demod_hop || L < 128 || L > 256 || ndata > 16) return false;
+  if (!bins_applicable(vec2_ok(x, nrec > 1 ? rec_stride : 0, L) && !(hop & 1), L, ndata, t_ds->lds_per_block))
+    return false;
+  if (hop % L || R % hop || (R / hop != 2 && R / hop != 4 && R / hop != 8)) return false;
+  return !std::is_same<XT, int16_t>::value || i16_int_fold<XT>(R, L);
+}
+
+// Whether the fallback gathers the windows first (demod_hop_device): the view lacks the pair
+// alignment that its gathered copy (rows of even R at an even L) would have.
+template <typename XT>
+bool hop_copied(const XT* x, int64_t rs, int R, int hop, int L) {
+  return L > 0 && !(L & 1) && !(R & 1) && !(vec2_ok(x, rs, L) && !(hop & 1));
+}
+
+// Segments per span: "demod_hop_span", or 4 V (a halo of (V - 1) / 4 V <= 1/4 of the span's own
+// blocks), halved while the launch would leave resident wave slots without a span.
+int hop_span(int V, int64_t nrec, int64_t nseg, int64_t slots) {
+  if (t_tune.demod_hop_span > 0) return t_tune.demod_hop_span;
+  int G = 4 * V;
+  while (G > 1 && nrec * ((nseg + G - 1) / G) < slots) G >>= 1;
+  return G;
+}
+
+template <typename XT, int V, bool ROWS>
+int launch_hop_t(const XT* x, int64_t nrec, int64_t rec_stride, int64_t nseg, int hop, int L, int ndata,
+                 const double* tab, double* qi, int64_t qi_ld, double* dc, hipStream_t st) {
+  auto kern = dfmi::demod_hop_kernel<XT, V, ROWS>;
+  const size_t lds = (size_t)2 * ndata * L * sizeof(double);
+  int per_cu = 0;
+  if (int orc = occupancy(kern, dfmi::kBlockThreads, lds, &per_cu)) return orc;
+  if (per_cu < 1) per_cu = 1;
+  const int G = hop_span(V, nrec, nseg, (int64_t)t_ds->n_cu * per_cu * dfmi::kWavesPerBlock);
+  const int64_t grid = bins_grid(t_ds->n_cu, per_cu, nrec * ((nseg + G - 1) / G));
+  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(dfmi::kBlockThreads), lds, st, x, nrec, rec_stride, nseg, hop, L,
+                     ndata, G, tab, qi, qi_ld, dc);
+  HIPCHK(hipGetLastError());
+  g_last_demod = std::string("demod_hop_kernel<") + (ROWS ? "rows" : "") + "> [" +
+                 (std::is_same<XT, double>::value ? "f64" : std::is_same<XT, float>::value ? "f32" : "i16 int") +
+                 ", V=" + std::to_string(V) + "]";
+  return DFMI_OK;
+}
+
+// Demodulation of nrec records' nseg overlapped segments each: column (rows: row) r·nseg + s.
+//   hop_native():  demod_hop_kernel;
+//   otherwise:     the planar kernels in place, record by record, at seg_stride = hop — they only
+//                  read x, and none of them assumes seg_stride >= R (the many-harmonic kernel's flat
+//                  stream needs seg_stride == R and folds segment by segment otherwise): the planar
+//                  string + " [hop in place]";
+//   except:        a view without the pair alignment its gathered copy would have (odd hop or
+//                  rec_stride, or an odd base, at even R and L) would take another kernel than the
+//                  planar call on that copy: its windows are gathered (widened) into "x_widen"
+//                  first and the double kernels run there: + " [hop copied]".
+// Both fallbacks give the bits of the planar typed call on the gathered copy.
+template <typename XT>
+int demod_hop_device(const XT* x, int64_t nrec, int64_t rec_stride, int64_t nseg, int R, int hop, int ndata,
+                     double w0, int period, double* qi, int64_t qi_ld, double* dc, hipStream_t st, bool rows) {
+  int L = period;
+  if (L == 0) L = detect_period_impl(w0, R, ndata);
+  const int64_t rs = nrec > 1 ? rec_stride : 0;
+  if (hop_native(x, nrec, rec_stride, R, hop, L, ndata)) {
+    const double* tab = nullptr;
+    if (int rc = basis_table(L, ndata, w0, &tab)) return rc;
+    auto go = [&](auto xp) {
+      using T = std::remove_cv_t<std::remove_pointer_t<decltype(xp)>>;
+#define DFMI_HOP(V_)                                                                                  \
+  return rows ? launch_hop_t<T, V_, true>(xp, nrec, rs, nseg, hop, L, ndata, tab, qi, qi_ld, dc, st)  \
+              : launch_hop_t<T, V_, false>(xp, nrec, rs, nseg, hop, L, ndata, tab, qi, qi_ld, dc, st)
+      if (R / hop == 2) DFMI_HOP(2);
+      if (R / hop == 4) DFMI_HOP(4);
+      DFMI_HOP(8);
+#undef DFMI_HOP
+    };
+    if constexpr (std::is_same<XT, int16_t>::value) return go((const dfmi::I16Int*)x);
+    else return go(x);
+  }
+  const bool copied = hop_copied(x, rs, R, hop, L);
+  for (int64_t r = 0; r < nrec; ++r) {
+    double* q = rows ? qi + r * nseg * qi_ld : qi + r * nseg;
+    double* d = rows ? nullptr : dc + r * nseg;
+    int rc;
+    if (copied) {
+      const double* xd = nullptr;
+      int64_t sd = 0;
+      if ((rc = widen_rows(x + r * rs, nseg, hop, R, st, &xd, &sd))) return rc;
+      rc = demod_device(xd, nseg, sd, R, ndata, w0, period, q, qi_ld, d, st, rows);
+    } else {
+      rc = demod_device(x + r * rs, nseg, hop, R, ndata, w0, period, q, qi_ld, d, st, rows);
+    }
+    if (rc) return rc;
+  }
+  g_last_demod += copied ? " [hop copied]" : " [hop in place]";
+  return DFMI_OK;
+}
+
 // The record pipeline's demodulation input when the records arrive as frames (nls_record_device).
 struct FramesIn {
   const int16_t* x;
@@ -1278,7 +1382,9 @@ template <typename XT>
 int nls_record_device(const XT* x, int64_t nrec, int64_t rec_stride, int64_t nbuf, int R, int ndata,
                       double w0, int period, const double* init_guess_host, int parallel, int64_t nchunk,
                       const dfmi_lm_config& cfg, const dfmi::LMConst& c, double* out, int32_t* fitok,
-                      hipStream_t st, const FramesIn* fr = nullptr) {
+                      hipStream_t st, const FramesIn* fr = nullptr, int hop = 0) {
+  // hop > 0 (dfmi_nls_record_hop): the nbuf segments of a record overlap, segment b at b·hop; the
+  // seed runs on segment 0 beside demod_hop_device, then the LM as in the two-kernel sequence below
   // fr (frames_native() holds): the nrec = fr->nch records arrive as frames at fr->x and x is
   // the planar copy of their seed buffers (rec_stride R); the seed runs on x beside
   // demod_frames_kernel on the frames, everything else is the two-kernel sequence below
@@ -1312,11 +1418,16 @@ int nls_record_device(const XT* x, int64_t nrec, int64_t rec_stride, int64_t nbu
   int L = period;
   if (L == 0) L = detect_period_impl(w0, R, ndata);
   const bool even_recs = nrec == 1 || (rec_stride % 2) == 0;
-  const bool wide = L > 0 && even_recs && wide_first(ndata, R) && wide_geometry(vec2_ok(x, R, L), L, ndata);
-  const bool rows = parallel && (nbuf <= 1 || nchunk >= nbuf - 1) && even_recs && !wide &&
-                    rows_supported(x, R, R, ndata, w0, period);
+  const bool hop_nat = hop && hop_native(x, nrec, rec_stride, R, hop, L, ndata);
+  // (a gathered copy of overlapped windows has the alignment of a contiguous record)
+  const bool hop_al = hop && !hop_nat && hop_copied(x, nrec > 1 ? rec_stride : 0, R, hop, L);
+  const bool wide = L > 0 && (even_recs || hop_al) && !hop_nat && wide_first(ndata, R) &&
+                    wide_geometry(hop_al || vec2_ok(x, R, L), L, ndata);
+  const bool rows = parallel && (nbuf <= 1 || nchunk >= nbuf - 1) && (even_recs || hop_al) && !wide &&
+                    (hop_nat || (hop_al ? bins_applicable(true, L, ndata, t_ds->lds_per_block)
+                                        : rows_supported(x, R, R, ndata, w0, period)));
   const int64_t qs = rows ? dfmi_row_stride(ndata) : 0;
-  if (!fr && parallel && rows && (nrec == 1 || rec_stride == nbuf * (int64_t)R) && nbuf > 1) {
+  if (!fr && !hop && parallel && rows && (nrec == 1 || rec_stride == nbuf * (int64_t)R) && nbuf > 1) {
     // ONE launch: the seeds (buffer 0 of every record) + the bulk demodulation; the LM
     // follows in stream order
     const double* tab = nullptr;
@@ -1359,6 +1470,8 @@ int nls_record_device(const XT* x, int64_t nrec, int64_t rec_stride, int64_t nbu
   }
   if (fr) {
     rc = launch_frames(fr->x, fr->nch, nbuf, R, L, ndata, w0, qi, rows ? qs : nseg, dc, st, rows);
+  } else if (hop) {
+    rc = demod_hop_device(x, nrec, rec_stride, nbuf, R, hop, ndata, w0, period, qi, rows ? qs : nseg, dc, st, rows);
   } else if (rec_stride == nbuf * (int64_t)R || nrec == 1) {
     rc = rows ? demod_device(x, nseg, R, R, ndata, w0, period, qi, qs, nullptr, st, true)
               : demod_device(x, nseg, R, R, ndata, w0, period, qi, nseg, dc, st);
@@ -1415,6 +1528,8 @@ const std::map<std::string, Knob>& knobs() {
       {"demod_wide_half", {&Tuning::demod_wide_half, {0, 1}}},
       {"demod_i16_int", {&Tuning::demod_i16_int, {0, 1}}},
       {"demod_frames", {&Tuning::demod_frames, {0, 1}}},
+      {"demod_hop", {&Tuning::demod_hop, {0, 1}}},
+      {"demod_hop_span", {&Tuning::demod_hop_span, {}}},
       {"demod_wide_dbg", {&Tuning::demod_wide_dbg, {0, 1, 2, 3, 4, 5, 6, 7}}},
       {"ekf_row", {&Tuning::ekf_row, {}}},
       {"ekf_rot", {&Tuning::ekf_rot, {0, 1}}},
@@ -2034,6 +2149,71 @@ int nls_record_frames_impl(const XT* x, int32_t nch, int64_t fs, int64_t nbuf, i
 int bad_xtype(int32_t xtype) {
   return xtype != DFMI_F64 && xtype != DFMI_F32 && xtype != DFMI_I16;
 }
+
+// Bodies of dfmi_demod_hop / dfmi_nls_record_hop over the sample type XT (hop < R; hop == R is
+// forwarded to the typed calls by the entry points).
+int bad_hop(int64_t nrec, int64_t rec_stride, int64_t nseg, int32_t R, int32_t hop, int32_t ndata) {
+  if (nrec < 0 || nseg < 0 || R <= 0 || ndata <= 0) return fail(DFMI_ERR_ARG, "bad hop geometry");
+  if (hop < 1 || hop > R) return fail(DFMI_ERR_ARG, "hop: 1 <= hop <= R");
+  if (nrec > 1 && rec_stride < (nseg - 1) * (int64_t)hop + R) return fail(DFMI_ERR_ARG, "rec_stride < (nseg-1)*hop + R");
+  return DFMI_OK;
+}
+
+template <typename XT>
+int demod_hop_impl(const XT* x, int64_t nrec, int64_t rec_stride, int64_t nseg, int32_t R, int32_t hop, int32_t ndata,
+                   double w0, int32_t period, double* qi, double* dc, int32_t mem, void* stream) {
+  CallScope cs(stream);
+  const int64_t ntot = nrec * nseg;
+  if (ntot > 0 && (!x || !qi || !dc)) return fail(DFMI_ERR_ARG, "null pointer");
+  int rc = ensure_init();
+  if (rc) return rc;
+  if (ntot == 0) return DFMI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  Staging sg(mem, st);
+  const int64_t ext = (nseg - 1) * (int64_t)hop + R;  // samples of one record
+  const int64_t rs = nrec > 1 ? rec_stride : ext;
+  const XT* dx;
+  double *dq, *dd;
+  if ((rc = sg.in("d_x", x, (size_t)((nrec - 1) * rs + ext) * sizeof(XT), &dx))) return rc;
+  if ((rc = sg.out("d_qi", qi, (size_t)2 * ndata * ntot * 8, &dq))) return rc;
+  if ((rc = sg.out("d_dc", dc, (size_t)ntot * 8, &dd))) return rc;
+  if ((rc = demod_hop_device(dx, nrec, rs, nseg, R, hop, ndata, w0, period, dq, ntot, dd, st, false))) return rc;
+  return sg.finish();
+}
+
+template <typename XT>
+int nls_record_hop_impl(const XT* x, int64_t nrec, int64_t rec_stride, int64_t nseg, int32_t R, int32_t hop,
+                        int32_t ndata, double w0, int32_t period, const double* init_guess, int32_t parallel,
+                        int64_t nchunk, const dfmi_lm_config* cfg, double* out, int32_t* fitok, int32_t mem,
+                        void* stream) {
+  CallScope cs(stream);
+  const int64_t ntot = nrec * nseg;
+  if (ntot > 0 && (!x || !init_guess || !out || !fitok)) return fail(DFMI_ERR_ARG, "null pointer");
+  dfmi_lm_config dcfg;
+  if (!cfg) {
+    dfmi_lm_config_default(&dcfg);
+    cfg = &dcfg;
+  }
+  dfmi::LMConst c;
+  int rc = to_lmconst(cfg, &c);
+  if (rc) return rc;
+  if ((rc = ensure_init())) return rc;
+  if (ntot == 0) return DFMI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  Staging sg(mem, st);
+  const int64_t ext = (nseg - 1) * (int64_t)hop + R;
+  const int64_t rs = nrec > 1 ? rec_stride : ext;
+  const XT* dx;
+  double* dout;
+  int32_t* dst;
+  if ((rc = sg.in("n_x", x, (size_t)((nrec - 1) * rs + ext) * sizeof(XT), &dx))) return rc;
+  if ((rc = sg.out("n_out", out, (size_t)6 * ntot * 8, &dout))) return rc;
+  if ((rc = sg.out("n_status", fitok, (size_t)ntot * 4, &dst))) return rc;
+  if ((rc = nls_record_device(dx, nrec, rs, nseg, R, ndata, w0, period, init_guess, parallel, nchunk, *cfg, c, dout, dst,
+                              st, nullptr, hop)))
+    return rc;
+  return sg.finish();
+}
 }  // namespace
 
 extern "C" {
@@ -2248,6 +2428,38 @@ int dfmi_nls_record_frames(const void* x, int32_t xtype, int32_t nch, int64_t fr
                                   parallel, nchunk, cfg, out, fitok, mem, stream);
   return nls_record_frames_impl((const float*)x, nch, frame_stride, nbuf, R, ndata, w0, period, init_guess, parallel,
                                 nchunk, cfg, out, fitok, mem, stream);
+}
+
+int dfmi_demod_hop(const void* x, int32_t xtype, int64_t nrec, int64_t rec_stride, int64_t nseg, int32_t R, int32_t hop,
+                   int32_t ndata, double w0, int32_t period, double* qi, double* dc, int32_t mem, void* stream) {
+  if (bad_xtype(xtype)) return fail(DFMI_ERR_ARG, "unknown sample type");
+  if (int rc = bad_hop(nrec, rec_stride, nseg, R, hop, ndata)) return rc;
+  if (hop == R && (nrec <= 1 || rec_stride == nseg * (int64_t)R))  // disjoint buffers: the planar call itself
+    return dfmi_demod_typed(x, xtype, nrec * nseg, R, R, ndata, w0, period, qi, dc, mem, stream);
+  if (xtype == DFMI_F64)
+    return demod_hop_impl((const double*)x, nrec, rec_stride, nseg, R, hop, ndata, w0, period, qi, dc, mem, stream);
+  if (xtype == DFMI_I16)
+    return demod_hop_impl((const int16_t*)x, nrec, rec_stride, nseg, R, hop, ndata, w0, period, qi, dc, mem, stream);
+  return demod_hop_impl((const float*)x, nrec, rec_stride, nseg, R, hop, ndata, w0, period, qi, dc, mem, stream);
+}
+
+int dfmi_nls_record_hop(const void* x, int32_t xtype, int64_t nrec, int64_t rec_stride, int64_t nseg, int32_t R,
+                        int32_t hop, int32_t ndata, double w0, int32_t period, const double* init_guess,
+                        int32_t parallel, int64_t nchunk, const dfmi_lm_config* cfg, double* out, int32_t* fitok,
+                        int32_t mem, void* stream) {
+  if (bad_xtype(xtype)) return fail(DFMI_ERR_ARG, "unknown sample type");
+  if (int rc = bad_hop(nrec, rec_stride, nseg, R, hop, ndata)) return rc;
+  if (hop == R)  // disjoint buffers: the typed call itself
+    return dfmi_nls_record_typed(x, xtype, nrec, rec_stride, nseg, R, ndata, w0, period, init_guess, parallel, nchunk, cfg,
+                                 out, fitok, mem, stream);
+  if (xtype == DFMI_F64)
+    return nls_record_hop_impl((const double*)x, nrec, rec_stride, nseg, R, hop, ndata, w0, period, init_guess, parallel,
+                               nchunk, cfg, out, fitok, mem, stream);
+  if (xtype == DFMI_I16)
+    return nls_record_hop_impl((const int16_t*)x, nrec, rec_stride, nseg, R, hop, ndata, w0, period, init_guess,
+                               parallel, nchunk, cfg, out, fitok, mem, stream);
+  return nls_record_hop_impl((const float*)x, nrec, rec_stride, nseg, R, hop, ndata, w0, period, init_guess, parallel,
+                             nchunk, cfg, out, fitok, mem, stream);
 }
 
 int32_t dfmi_qi_row_stride(int32_t ndata) { return ndata > 0 ? dfmi_row_stride((int)ndata) : 0; }

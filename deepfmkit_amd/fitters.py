@@ -116,9 +116,16 @@ def _segment_errors(lib, out, nseg, ndata, mem, stream):
 
 
 def nls_records(records, f_samp, f_mod, R, nbuf, ndata=10, init_guess=(1.6, 6.0, 0.0, 0.0), parallel=True,
-                n_cores=None, errors=False):
+                n_cores=None, errors=False, hop=None):
     """Run the StandardNLSFitter pipeline on one or more equal-length records in ONE
     GPU call (config 3: several channels as one batch).
+
+    hop (samples, 1 <= hop <= R; None or R: disjoint buffers, the call as it always was): a
+    sliding-window readout, segment s of a record at samples [s*hop, s*hop + R)
+    (dfmi_nls_record_hop, include/dfmi.h). nbuf is then the number of segments per record, or
+    None for all that fit, (n_samples - R)//hop + 1; the result series runs at f_samp/hop with the
+    noise of an R-sample fit. Overlapped points share samples, so neighbouring points are
+    CORRELATED: an average or a spectrum of them must not count them as independent.
 
     records: list of 1-D float64, float32 or int16 arrays (host) or CUDA tensors, or a 2-D
     array/tensor (nrec, >= nbuf*R). float32 and int16 records go to dfmi_nls_record_typed as they
@@ -134,14 +141,23 @@ def nls_records(records, f_samp, f_mod, R, nbuf, ndata=10, init_guess=(1.6, 6.0,
         _check_errors_ndata(ndata)
     lib = _lib.load()
     w0 = w0_of(f_mod, f_samp)
+    hop = None if hop is None or int(hop) == R else int(hop)
+    if hop is not None:
+        if not 1 <= hop <= R:
+            raise ValueError(f"hop must be within 1..R = {R}, got {hop}")
+        n_samples = int(records[0].shape[0] if isinstance(records, (list, tuple)) else records.shape[-1])
+        nbuf = max((n_samples - R) // hop + 1, 0) if nbuf is None else int(nbuf)
+        if n_samples < (nbuf - 1) * hop + R:
+            raise ValueError("records shorter than (nbuf-1)*hop + R")
+    ext = nbuf * R if hop is None else (nbuf - 1) * hop + R  # samples of a record the call reads
     if isinstance(records, (list, tuple)):
         if _is_device_tensor(records[0]):
             import torch
-            x = torch.stack([r[: nbuf * R] for r in records]).contiguous()
+            x = torch.stack([r[:ext] for r in records]).contiguous()
         else:
             recs = [_host_samples(r) for r in records]
             dt = recs[0].dtype if all(r.dtype == recs[0].dtype for r in recs) else np.float64
-            x = np.ascontiguousarray(np.stack([r[: nbuf * R] for r in recs]), dtype=dt)
+            x = np.ascontiguousarray(np.stack([r[:ext] for r in recs]), dtype=dt)
     else:
         x = records
     if not _is_device_tensor(x):
@@ -165,7 +181,11 @@ def nls_records(records, f_samp, f_mod, R, nbuf, ndata=10, init_guess=(1.6, 6.0,
         ok = torch.empty(nseg, dtype=torch.int32, device=x.device)
         mark("alloc")
         with _on_device(x):
-            if xtype == _lib.DFMI_F64:
+            if hop is not None:
+                rc = lib.dfmi_nls_record_hop(x.data_ptr(), xtype, nrec, rec_stride, nbuf, R, hop, ndata, w0, 0,
+                                             _lib.ptr(g), 1 if parallel else 0, max(nchunk, 1), cfg, out.data_ptr(),
+                                             ok.data_ptr(), _lib.DFMI_MEM_DEVICE, _torch_stream(x.device))
+            elif xtype == _lib.DFMI_F64:
                 rc = lib.dfmi_nls_record(x.data_ptr(), nrec, rec_stride, nbuf, R, ndata, w0, 0, _lib.ptr(g),
                                          1 if parallel else 0, max(nchunk, 1), cfg, out.data_ptr(), ok.data_ptr(),
                                          _lib.DFMI_MEM_DEVICE, _torch_stream(x.device))
@@ -183,7 +203,11 @@ def nls_records(records, f_samp, f_mod, R, nbuf, ndata=10, init_guess=(1.6, 6.0,
         return out, ok
     out = np.empty((6, nseg))
     ok = np.empty(nseg, dtype=np.int32)
-    if x.dtype != np.float64:
+    if hop is not None:
+        rc = lib.dfmi_nls_record_hop(_lib.ptr(x), _xtype(x.dtype), nrec, rec_stride, nbuf, R, hop, ndata, w0, 0,
+                                     _lib.ptr(g), 1 if parallel else 0, max(nchunk, 1), cfg, _lib.ptr(out),
+                                     _lib.ptr(ok), _lib.DFMI_MEM_HOST, None)
+    elif x.dtype != np.float64:
         rc = lib.dfmi_nls_record_typed(_lib.ptr(x), _xtype(x.dtype), nrec, rec_stride, nbuf, R, ndata, w0, 0,
                                        _lib.ptr(g), 1 if parallel else 0, max(nchunk, 1), cfg, _lib.ptr(out),
                                        _lib.ptr(ok), _lib.DFMI_MEM_HOST, None)
@@ -457,7 +481,9 @@ class StandardNLSFitter(BaseFitter):
     parallel=False follows _fit_sequential (one warm-start chain).
     errors=True appends the float64 columns amp_err, m_err, phi_err, psi_err after fitok: the
     standard errors sqrt(diag(ssq/(2 ndata - 4) (J^T J)^-1)) at each buffer's fitted parameters
-    (dfmi_fisher on the device, behind the fit; needs ndata >= 3)."""
+    (dfmi_fisher on the device, behind the fit; needs ndata >= 3).
+    hop=k (samples, k < R): a sliding-window readout, one point per k samples from windows of R
+    (nls_records' hop; neighbouring points are correlated); not with devices=."""
 
     def fit(self, main_raw, **kwargs) -> pd.DataFrame:
         n = self.config["n"]
@@ -474,6 +500,17 @@ class StandardNLSFitter(BaseFitter):
             return pd.DataFrame()
         x = main_raw.samples()
         N = int(x.shape[0])
+        hop = kwargs.get("hop")
+        if hop is not None and int(hop) != R:
+            if kwargs.get("devices") is not None:
+                raise ValueError("hop= runs on the current GPU: not with devices=")
+            xs = x if _is_device_tensor(x) else _host_samples(x)
+            if _is_device_tensor(xs) and N > 1 and xs.stride(0) != 1:
+                xs = xs.contiguous()  # a column of a frames block
+            res = nls_records(xs.reshape(1, N), main_raw.f_samp, main_raw.f_mod, R, None, ndata,
+                              (init_a, init_m, 0.0, init_psi), parallel=parallel,
+                              n_cores=kwargs.get("n_cores") if parallel else None, errors=errors, hop=int(hop))
+            return frame_with_errors(*res) if errors else frame_from(*res, tau_divisor(main_raw))
         if N % R != 0:
             # the reference reshapes the whole column with reshape(-1, R) (fitters.py:375, 412)
             raise ValueError(f"cannot reshape array of size {N} into shape ({R})")

@@ -207,6 +207,38 @@ int dfmi_nls_record_frames(const void* x, int32_t xtype, int32_t nch, int64_t fr
                            int64_t nchunk, const dfmi_lm_config* cfg, double* out, int32_t* fitok,
                            int32_t mem, void* stream);
 
+/* Overlapped segments (a sliding-window readout): segment s < nseg of record r < nrec is
+ * x[r * rec_stride + s * hop + t], t < R, so consecutive segments share R - hop samples and the
+ * result series runs at f_samp / hop with the noise of an R-sample fit (neighbouring points are
+ * correlated). dfmi_demod_hop and dfmi_nls_record_hop give what dfmi_demod_typed (nrec * nseg
+ * segments) and dfmi_nls_record_typed (nbuf := nseg) give on the gathered copy
+ * y[r][s * R + t] = x[r][s * hop + t]: the same layouts (column r * nseg + s), the same meaning of
+ * parallel and nchunk, local time t = 0..R-1 in every segment, segment 0 the seed buffer.
+ * DFMI_ERR_ARG: hop < 1 or hop > R, nrec > 1 with rec_stride < (nseg - 1) * hop + R, an unknown
+ * xtype. hop == R forwards to the typed call. DFMI_MEM_HOST stages each record once, in its own
+ * type ((nseg - 1) * hop + R samples), never the gathered copy.
+ * demod_hop_kernel folds every hop block (hop samples) once and sums the V = R / hop blocks of a
+ * segment in registers, reported as "demod_hop_kernel<...> [f64|f32|i16 int, V=...]", when
+ *   - the basis period L (given or detected) is even, 128 <= L <= 256, with at most 16 harmonics,
+ *   - hop % L == 0 and V is 2, 4 or 8,
+ *   - x and rec_stride are aligned to sample pairs (dfmi_demod_typed's vector-pair condition),
+ *   - int16: ceil(R / L) <= 65535 (the integer fold), and the tuning key "demod_hop" is not 0.
+ * int16 records then give the planar call's bits on the gathered copy whenever that call runs the
+ * bin kernels (integer sums are exact in any order); float and double records agree with it to
+ * rounding (a segment's bins are summed block by block, oldest first; the bits do not depend on
+ * the span size, tuning key "demod_hop_span"). Everything else runs the planar kernels in place at
+ * seg_stride = hop, record by record (" [hop in place]"), or, for a view without the pair
+ * alignment its gathered copy would have, on a gathered copy (" [hop copied]"): the definition's
+ * bits (one exception: odd R at an even hop keeps the pair-aligned kernels in place, where the
+ * many-harmonic kernel's QI differ from the fold kernel's in the last bits). */
+int dfmi_demod_hop(const void* x, int32_t xtype, int64_t nrec, int64_t rec_stride, int64_t nseg, int32_t R,
+                   int32_t hop, int32_t ndata, double w0, int32_t period, double* qi, double* dc, int32_t mem,
+                   void* stream);
+int dfmi_nls_record_hop(const void* x, int32_t xtype, int64_t nrec, int64_t rec_stride, int64_t nseg, int32_t R,
+                        int32_t hop, int32_t ndata, double w0, int32_t period, const double* init_guess,
+                        int32_t parallel, int64_t nchunk, const dfmi_lm_config* cfg, double* out, int32_t* fitok,
+                        int32_t mem, void* stream);
+
 /* Per-sample EKF (fitters.py:214-320) over nrec independent channels, each a serial
  * chain over its samples: up to 16 x CUs channels one 16-lane DPP row per channel (4 per
  * wave; ekf_rot_kernel with sin / cos by rotation between anchors when R % 4 == 0, else
