@@ -428,6 +428,18 @@ __device__ __forceinline__ void stage_table(const double* __restrict__ tab, doub
   if ((n & 1) && tid == 0) lds[n - 1] = tab[n - 1];
 }
 
+// The same table by LDS-DMA: wave `wave` of nwaves issues its 1-KB blocks (lane l's 16 bytes of
+// block k land at lds + 128 k + 2 l) and returns with them in flight, holding no register.
+// The caller waits (vmcnt) before the barrier that publishes the table. n even, tab 16-B aligned.
+__device__ __forceinline__ void stage_table_dma(const double* __restrict__ tab, double* lds, int n, int lane,
+                                                int wave, int nwaves) {
+  const int n2 = n / 2;
+  for (int k = wave; k * 64 < n2; k += nwaves) {
+    const int i = k * 64 + lane;
+    if (i < n2) __builtin_amdgcn_global_load_lds((const void*)(tab + 2 * i), (void*)(lds + 128 * k), 16, 0, 0);
+  }
+}
+
 template <int VEC, int MAXSLOT, bool LDS_TAB, int LOADS = 8, bool NT = true>
 __global__ __launch_bounds__(kBlockThreads) void demod_fold_kernel(
     const double* __restrict__ x, int64_t nseg, int64_t seg_stride, int R, int L, int ndata,
@@ -474,13 +486,13 @@ __global__ __launch_bounds__(kBlockThreads) void demod_fold_kernel(
 // the next segment's first PFN chunks (at `next`, if not null) are issued into pf
 // before this segment's contraction, so the wave has loads in flight while it
 // contracts.
-template <int MAXSLOT, int LOADS, bool NT, int HB, bool ROWS, int PFN = 0, bool ROW_LDS = false, typename XT = double>
-__device__ __forceinline__ void bins_segment(const XT* __restrict__ xs0, int R, int L, int ndata,
-                                             const double* __restrict__ T, double* __restrict__ ybin, int lane,
-                                             const bool (&pval)[MAXSLOT], const int (&pbase)[MAXSLOT],
-                                             double* __restrict__ qi, int64_t qi_ld, int64_t col,
-                                             double* __restrict__ dc, double (*pf)[2] = nullptr,
-                                             const XT* __restrict__ next = nullptr) {
+// The segment comes in two parts, bins_fold (everything up to and including the next segment's
+// prefetch) and bins_finish (the contraction): the bulk kernel's workgroup barrier stands
+// between them in a wave's first segment (bins_kernel_body).
+template <int MAXSLOT, int LOADS, bool NT, int PFN, typename XT>
+__device__ __forceinline__ void bins_fold(const XT* __restrict__ xs0, int R, int L, double* __restrict__ ybin,
+                                          int lane, const bool (&pval)[MAXSLOT], const int (&pbase)[MAXSLOT],
+                                          double (*pf)[2], const XT* __restrict__ next) {
   typedef double d2v __attribute__((ext_vector_type(2)));
   const int nch = R >> 7;           // full 128-sample chunks
   const int tail = R - (nch << 7);  // samples of the last, partial chunk
@@ -564,6 +576,14 @@ __device__ __forceinline__ void bins_segment(const XT* __restrict__ xs0, int R, 
       }
     }
   }
+}
+
+template <int MAXSLOT, int HB, bool ROWS, bool ROW_LDS = false>
+__device__ __forceinline__ void bins_finish(int R, int L, int ndata, const double* __restrict__ T,
+                                            const double* __restrict__ ybin, int lane, const bool (&pval)[MAXSLOT],
+                                            const int (&pbase)[MAXSLOT], double* __restrict__ qi, int64_t qi_ld,
+                                            int64_t col, double* __restrict__ dc) {
+  typedef double d2v __attribute__((ext_vector_type(2)));
   double y[MAXSLOT][2];
 #pragma unroll
   for (int j = 0; j < MAXSLOT; ++j) {
@@ -576,6 +596,17 @@ __device__ __forceinline__ void bins_segment(const XT* __restrict__ xs0, int R, 
     }
   }
   fold_finish<2, MAXSLOT, HB, ROWS, ROW_LDS>(y, pval, pbase, R, L, ndata, T, lane, qi, qi_ld, col, dc);
+}
+
+template <int MAXSLOT, int LOADS, bool NT, int HB, bool ROWS, int PFN = 0, bool ROW_LDS = false, typename XT = double>
+__device__ __forceinline__ void bins_segment(const XT* __restrict__ xs0, int R, int L, int ndata,
+                                             const double* __restrict__ T, double* __restrict__ ybin, int lane,
+                                             const bool (&pval)[MAXSLOT], const int (&pbase)[MAXSLOT],
+                                             double* __restrict__ qi, int64_t qi_ld, int64_t col,
+                                             double* __restrict__ dc, double (*pf)[2] = nullptr,
+                                             const XT* __restrict__ next = nullptr) {
+  bins_fold<MAXSLOT, LOADS, NT, PFN, XT>(xs0, R, L, ybin, lane, pval, pbase, pf, next);
+  bins_finish<MAXSLOT, HB, ROWS, ROW_LDS>(R, L, ndata, T, ybin, lane, pval, pbase, qi, qi_ld, col, dc);
 }
 
 // int16 counts folded by INTEGER accumulation. Every partial sum of int16 values is an exact
@@ -622,18 +653,17 @@ __device__ __forceinline__ void iacc_prefetch(const int16_t* __restrict__ xs, in
 // bins_segment for I16Int: one segment folded into the lane's int32 bins, then fold_finish.
 // PFN > 0: the first PFN cycles arrive prefetched in pf (R / L >= PFN) and the next segment's
 // (at `next`, if not null) are issued before the contraction, as bins_segment does with chunks.
-template <int MAXSLOT, int LOADS, int HB, bool ROWS, int PFN = 0, bool ROW_LDS = false>
-__device__ __forceinline__ void bins_segment_iacc(const int16_t* __restrict__ xs, int R, int L, int ndata,
-                                                  const double* __restrict__ T, int lane,
-                                                  const bool (&pval)[MAXSLOT], const int (&pbase)[MAXSLOT],
-                                                  const int (&poff)[MAXSLOT], const int32_t (&pmask)[MAXSLOT],
-                                                  double* __restrict__ qi, int64_t qi_ld, int64_t col,
-                                                  double* __restrict__ dc, int32_t (*pf)[MAXSLOT] = nullptr,
-                                                  const int16_t* __restrict__ next = nullptr) {
+// As bins_segment, in two parts: bins_fold_iacc leaves the lane's integer bins in yi,
+// bins_finish_iacc converts and contracts them.
+template <int MAXSLOT, int LOADS, int PFN>
+__device__ __forceinline__ void bins_fold_iacc(const int16_t* __restrict__ xs, int R, int L,
+                                               const bool (&pval)[MAXSLOT], const int (&pbase)[MAXSLOT],
+                                               const int (&poff)[MAXSLOT], const int32_t (&pmask)[MAXSLOT],
+                                               int32_t (&yi)[MAXSLOT][2], int32_t (*pf)[MAXSLOT],
+                                               const int16_t* __restrict__ next) {
   constexpr int UNR = (MAXSLOT >= LOADS) ? 1 : (LOADS / MAXSLOT);  // cycles per load group
   const int ncyc = R / L;
   const int rem = R - ncyc * L;
-  int32_t yi[MAXSLOT][2];
 #pragma unroll
   for (int j = 0; j < MAXSLOT; ++j) yi[j][0] = yi[j][1] = 0;
   auto add_pair = [&](int j, int32_t w) {
@@ -691,6 +721,13 @@ __device__ __forceinline__ void bins_segment_iacc(const int16_t* __restrict__ xs
   if constexpr (PFN > 0) {
     if (next) iacc_prefetch<MAXSLOT, PFN>(next, L, poff, pf);
   }
+}
+
+template <int MAXSLOT, int HB, bool ROWS, bool ROW_LDS = false>
+__device__ __forceinline__ void bins_finish_iacc(int R, int L, int ndata, const double* __restrict__ T, int lane,
+                                                 const bool (&pval)[MAXSLOT], const int (&pbase)[MAXSLOT],
+                                                 const int32_t (&yi)[MAXSLOT][2], double* __restrict__ qi,
+                                                 int64_t qi_ld, int64_t col, double* __restrict__ dc) {
   double y[MAXSLOT][2];
 #pragma unroll
   for (int j = 0; j < MAXSLOT; ++j) {
@@ -700,14 +737,46 @@ __device__ __forceinline__ void bins_segment_iacc(const int16_t* __restrict__ xs
   fold_finish<2, MAXSLOT, HB, ROWS, ROW_LDS>(y, pval, pbase, R, L, ndata, T, lane, qi, qi_ld, col, dc);
 }
 
+template <int MAXSLOT, int LOADS, int HB, bool ROWS, int PFN = 0, bool ROW_LDS = false>
+__device__ __forceinline__ void bins_segment_iacc(const int16_t* __restrict__ xs, int R, int L, int ndata,
+                                                  const double* __restrict__ T, int lane,
+                                                  const bool (&pval)[MAXSLOT], const int (&pbase)[MAXSLOT],
+                                                  const int (&poff)[MAXSLOT], const int32_t (&pmask)[MAXSLOT],
+                                                  double* __restrict__ qi, int64_t qi_ld, int64_t col,
+                                                  double* __restrict__ dc, int32_t (*pf)[MAXSLOT] = nullptr,
+                                                  const int16_t* __restrict__ next = nullptr) {
+  int32_t yi[MAXSLOT][2];
+  bins_fold_iacc<MAXSLOT, LOADS, PFN>(xs, R, L, pval, pbase, poff, pmask, yi, pf, next);
+  bins_finish_iacc<MAXSLOT, HB, ROWS, ROW_LDS>(R, L, ndata, T, lane, pval, pbase, yi, qi, qi_ld, col, dc);
+}
+
 // One wavefront per segment (grid-stride over 4-wave workgroups that share one LDS
 // copy of the basis); each wave's L bins follow the basis in LDS. LOADS 1-KB chunk
 // loads per lane in flight (non-temporal: the input is read once). ROWS selects the
 // output layout (fold_finish). PFN > 0 (and R >= 128·PFN): the next segment's first
 // PFN chunks are in flight during a segment's contraction (bins_segment).
+// The workgroup's first instructions are its waves' first sample loads. The basis follows them
+// by LDS-DMA (stage_table_dma: no registers, so the fold's budget is untouched; holding the
+// table in registers across the first fold costs the kernel a wave per SIMD), its round trip
+// through the memory queue the bulk stream keeps full passes behind a segment's worth of
+// samples, and the workgroup's one barrier stands immediately before the first contraction,
+// the first reader of the basis. Staged at entry (DFMI_BINS_LATE_STAGE 0, A/B builds) every
+// workgroup waits for that round trip with no sample bytes in flight. A wave reaches the
+// barrier exactly once: in its first segment or, when it has none, after the loops below.
+// hipcc inserts no wait for LDS written by DMA: vector memory loads return in order, so the
+// counted wait before the barrier (at most the next segment's NPF prefetch loads, issued
+// after the table's, still in flight) covers the wave's share.
 // probe (diagnostics, may be null): s_memrealtime at the entry of workgroups 0 and
-// gridDim-1 and at the exit of workgroup 0's wave 0 ([3], [4], [5]).
+// gridDim-1 and at the exit of workgroup 0's wave 0 ([3], [4], [5]); per workgroup below
+// kProbeGroups, wave 0's entry, first sample load issued (prefetch paths) and first contraction
+// begun ([kProbeStamps + k·kProbeGroups + workgroup], k = 0, 1, 2).
+#ifndef DFMI_BINS_LATE_STAGE
+#define DFMI_BINS_LATE_STAGE 1
+#endif
 constexpr int kProbeWaves = 16384;  // per-wave slots of the diagnostics probe buffer
+constexpr int kProbeGroups = kProbeWaves / kWavesPerBlock;  // per-workgroup slots
+constexpr int kProbeStamps = 16 + 2 * kProbeWaves;          // first per-workgroup stamp
+constexpr int kProbeWords = kProbeStamps + 3 * kProbeGroups;
 template <int MAXSLOT, int LOADS, bool ROWS, int PFN = 0, typename XT = double>
 __device__ __forceinline__ void bins_kernel_body(
     const XT* __restrict__ x, int64_t nseg, int64_t seg_stride, int R, int L, int ndata,
@@ -721,10 +790,18 @@ __device__ __forceinline__ void bins_kernel_body(
   }
   const int nwork = (int)gridDim.x - block0;
   if (bid < 0) return;
+  auto stamp = [&](int k) {
+    if (probe && threadIdx.x == 0 && bid < kProbeGroups)
+      probe[kProbeStamps + k * kProbeGroups + bid] = __builtin_amdgcn_s_memrealtime();
+  };
+  stamp(0);
+  constexpr bool kLate = DFMI_BINS_LATE_STAGE != 0;
   extern __shared__ __attribute__((aligned(16))) double lds_dyn[];
   const int ntab = 2 * ndata * L;
-  stage_table(tab, lds_dyn, ntab, threadIdx.x, kBlockThreads);
-  __syncthreads();
+  if constexpr (!kLate) {
+    stage_table(tab, lds_dyn, ntab, threadIdx.x, kBlockThreads);
+    __syncthreads();
+  }
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   double* __restrict__ ybin = lds_dyn + ntab + wave * L;  // this wave's L phase bins
@@ -737,40 +814,96 @@ __device__ __forceinline__ void bins_kernel_body(
     pval[j] = (j < nslot) && (pbase[j] < L);
   }
   const int64_t s0 = (int64_t)bid * kWavesPerBlock + wave, ds = (int64_t)nwork * kWavesPerBlock;
+  auto stage_late = [&] {
+    if constexpr (kLate) stage_table_dma(tab, lds_dyn, ntab, lane, wave, kWavesPerBlock);
+  };
+  bool first = true;  // wave-uniform: the wave's first segment is still to be contracted
+  // The wave's segments: fold(s) and finish(s) per segment, the barrier between them in the
+  // first. npf: loads of the next segment's prefetch that may be in flight at that point.
+  auto segments = [&](auto npf, auto&& fold, auto&& finish) {
+    for (int64_t s = s0; s < nseg; s += ds) {
+      fold(s);
+      if (first) {
+        if constexpr (kLate) {
+          // without a next segment nothing younger than the table is in flight: wait for all
+          if (s + ds < nseg) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(decltype(npf)::value) : "memory");
+          else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+          __syncthreads();
+        }
+        stamp(2);
+        first = false;
+      }
+      finish(s);
+    }
+  };
+  auto next_of = [&](auto* base, int64_t s) { return s + ds < nseg ? base + (s + ds) * seg_stride : nullptr; };
   if constexpr (std::is_same<XT, I16Int>::value) {
     // integer-accumulating fold (bins_segment_iacc): the same pipeline, in cycles
     const int16_t* __restrict__ xi = reinterpret_cast<const int16_t*>(x);
     int poff[MAXSLOT];
     int32_t pmask[MAXSLOT];
+    int32_t yi[MAXSLOT][2];
     iacc_lanes<MAXSLOT>(pval, pbase, poff, pmask);
+    auto finish = [&](int64_t s) {
+      bins_finish_iacc<MAXSLOT, kHarmBlock, ROWS>(R, L, ndata, lds_dyn, lane, pval, pbase, yi, qi, qi_ld, s, dc);
+    };
     if (PFN > 0 && R / L >= PFN) {
       int32_t pf[PFN > 0 ? PFN : 1][MAXSLOT];
       if (s0 < nseg) iacc_prefetch<MAXSLOT, PFN>(xi + s0 * seg_stride, L, poff, pf);
-      for (int64_t s = s0; s < nseg; s += ds)
-        bins_segment_iacc<MAXSLOT, LOADS, kHarmBlock, ROWS, PFN>(xi + s * seg_stride, R, L, ndata, lds_dyn, lane, pval,
-                                                                 pbase, poff, pmask, qi, qi_ld, s, dc, pf,
-                                                                 s + ds < nseg ? xi + (s + ds) * seg_stride : nullptr);
+      stage_late();
+      stamp(1);
+      segments(
+          std::integral_constant<int, PFN * MAXSLOT>{},
+          [&](int64_t s) {
+            bins_fold_iacc<MAXSLOT, LOADS, PFN>(xi + s * seg_stride, R, L, pval, pbase, poff, pmask, yi, pf,
+                                                next_of(xi, s));
+          },
+          finish);
     } else {
-      for (int64_t s = s0; s < nseg; s += ds)
-        bins_segment_iacc<MAXSLOT, LOADS, kHarmBlock, ROWS>(xi + s * seg_stride, R, L, ndata, lds_dyn, lane, pval, pbase,
-                                                            poff, pmask, qi, qi_ld, s, dc);
+      stage_late();
+      segments(
+          std::integral_constant<int, 0>{},
+          [&](int64_t s) {
+            bins_fold_iacc<MAXSLOT, LOADS, 0>(xi + s * seg_stride, R, L, pval, pbase, poff, pmask, yi, nullptr,
+                                              nullptr);
+          },
+          finish);
     }
-  } else if (PFN > 0 && (R >> 7) >= PFN) {
-    // software pipeline across this wave's segments (see bins_segment PFN)
-    double pf[PFN > 0 ? PFN : 1][2];
-    if (s0 < nseg) {
-      const XT* __restrict__ x0 = x + s0 * seg_stride + 2 * lane;
-#pragma unroll
-      for (int u = 0; u < PFN; ++u) SampleT<XT>::template load_nt<2>(x0 + u * 128, pf[u]);
-    }
-    for (int64_t s = s0; s < nseg; s += ds)
-      bins_segment<MAXSLOT, LOADS, true, kHarmBlock, ROWS, PFN, false, XT>(
-          x + s * seg_stride, R, L, ndata, lds_dyn, ybin, lane, pval, pbase, qi, qi_ld, s, dc, pf,
-          s + ds < nseg ? x + (s + ds) * seg_stride : nullptr);
   } else {
-    for (int64_t s = s0; s < nseg; s += ds)
-      bins_segment<MAXSLOT, LOADS, true, kHarmBlock, ROWS, 0, false, XT>(x + s * seg_stride, R, L, ndata, lds_dyn, ybin,
-                                                                         lane, pval, pbase, qi, qi_ld, s, dc);
+    auto finish = [&](int64_t s) {
+      bins_finish<MAXSLOT, kHarmBlock, ROWS>(R, L, ndata, lds_dyn, ybin, lane, pval, pbase, qi, qi_ld, s, dc);
+    };
+    if (PFN > 0 && (R >> 7) >= PFN) {
+      // software pipeline across this wave's segments (see bins_segment PFN)
+      double pf[PFN > 0 ? PFN : 1][2];
+      if (s0 < nseg) {
+        const XT* __restrict__ x0 = x + s0 * seg_stride + 2 * lane;
+#pragma unroll
+        for (int u = 0; u < PFN; ++u) SampleT<XT>::template load_nt<2>(x0 + u * 128, pf[u]);
+      }
+      stage_late();
+      stamp(1);
+      segments(
+          std::integral_constant<int, PFN>{},
+          [&](int64_t s) {
+            bins_fold<MAXSLOT, LOADS, true, PFN, XT>(x + s * seg_stride, R, L, ybin, lane, pval, pbase, pf,
+                                                     next_of(x, s));
+          },
+          finish);
+    } else {
+      stage_late();
+      segments(
+          std::integral_constant<int, 0>{},
+          [&](int64_t s) {
+            bins_fold<MAXSLOT, LOADS, true, 0, XT>(x + s * seg_stride, R, L, ybin, lane, pval, pbase, nullptr,
+                                                   (const XT*)nullptr);
+          },
+          finish);
+    }
+  }
+  if (kLate && first) {  // a wave without a segment: its share of the basis is all it waits for
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
   }
   if (probe && threadIdx.x == 0 && bid == 0) probe[5] = __builtin_amdgcn_s_memrealtime();
   // per-wave exit times (probe[16 + global wave], up to kProbeWaves waves) and the

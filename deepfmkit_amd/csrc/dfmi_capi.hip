@@ -68,8 +68,9 @@ std::mutex g_mu;  // the device map, HIP initialisation and the tuning knobs
 struct Tuning {
   int demod_kernel = 1;  // 1: bin-in-LDS kernel where it applies, 0: cycle-aligned fold kernel
   int lm_general = 0;    // 1: force the two-pass (general) LM path for every ndata
-  int demod_spw = 2;     // bin kernels: grid sized for ~this many segments per wave (0: one persistent
-                         // wave per slot); later workgroups go to the slots that free first
+  int demod_spw = -1;    // bin kernels: grid sized for ~this many segments per wave (0: one persistent
+                         // wave per slot); later workgroups go to the slots that free first. -1: the
+                         // kernel's own (kBinsSpw, kEntryStagedSpw)
   int demod_wide = 1;    // component-major QI where the bin kernel's LDS basis does not fit: 1 the
                          // many-harmonic kernel (demod_wide_kernel), 0 the fold kernel; 2 (A/B) the
                          // many-harmonic kernel wherever its geometry applies
@@ -635,12 +636,19 @@ int64_t persistent_grid(int n_cu, int per_cu, int64_t need) {
 // persistent wave per slot and a static segment list, waves finished between 448 and
 // 548 us (XCC and HBM-path dependent, profiles/r02j_demod_wave_finish.jsonl) and the
 // launch ended with the slowest; ~2 segments per wave measured best (0.513-0.516 vs
-// 0.533-0.535 ms, profiles/r02k_tune_spw.json).
-int64_t bins_grid(int n_cu, int per_cu, int64_t nseg) {
+// 0.533-0.535 ms, profiles/r02k_tune_spw.json) while every workgroup staged the basis before
+// its first sample load, as the frame and hop kernels still do. The bin kernels stage it behind
+// the first fold (demod.h bins_kernel_body), and there one segment per wave is ahead: the step
+// 0.5146 against 0.5261 ms at 2, 6.262 against 6.389 ms over 1.25 M segments
+// (profiles/r07/bins_prologue.md).
+constexpr int kBinsSpw = 1, kEntryStagedSpw = 2;
+int demod_spw(int own) { return t_tune.demod_spw < 0 ? own : t_tune.demod_spw; }
+
+int64_t bins_grid(int n_cu, int per_cu, int64_t nseg, int own_spw) {
   const int64_t need = (nseg + dfmi::kWavesPerBlock - 1) / dfmi::kWavesPerBlock;
   int64_t grid = persistent_grid(n_cu, per_cu, need);
-  if (t_tune.demod_spw > 0) {
-    const int64_t per = (int64_t)dfmi::kWavesPerBlock * t_tune.demod_spw;
+  if (const int spw = demod_spw(own_spw); spw > 0) {
+    const int64_t per = (int64_t)dfmi::kWavesPerBlock * spw;
     const int64_t want = (nseg + per - 1) / per;
     if (want > grid) grid = want;
   }
@@ -706,7 +714,7 @@ int launch_bins_t(const XT* x, int64_t nseg, int64_t stride, int R, int L, int n
   int per_cu = 0;
   if (int orc = occupancy(kern, dfmi::kBlockThreads, lds, &per_cu)) return orc;
   if (per_cu < 1) per_cu = 1;
-  const int64_t grid = bins_grid(n_cu, per_cu, nseg);
+  const int64_t grid = bins_grid(n_cu, per_cu, nseg, kBinsSpw);
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(dfmi::kBlockThreads), lds, st, x, nseg, stride, R, L, ndata,
                      tab, qi, qi_ld, dc, t_ds->probe);
   HIPCHK(hipGetLastError());
@@ -964,7 +972,7 @@ int launch_frames_t(const int16_t* x, int64_t nbuf, int R, int L, int ndata, con
   int per_cu = 0;
   if (int orc = occupancy(kern, dfmi::kBlockThreads, lds, &per_cu)) return orc;
   if (per_cu < 1) per_cu = 1;
-  const int64_t grid = bins_grid(t_ds->n_cu, per_cu, nbuf);
+  const int64_t grid = bins_grid(t_ds->n_cu, per_cu, nbuf, kEntryStagedSpw);
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(dfmi::kBlockThreads), lds, st, x, nbuf, R, L, ndata, tab, qi,
                      qi_ld, dc);
   HIPCHK(hipGetLastError());
@@ -1062,7 +1070,7 @@ int launch_hop_t(const XT* x, int64_t nrec, int64_t rec_stride, int64_t nseg, in
   if (int orc = occupancy(kern, dfmi::kBlockThreads, lds, &per_cu)) return orc;
   if (per_cu < 1) per_cu = 1;
   const int G = hop_span(V, nrec, nseg, (int64_t)t_ds->n_cu * per_cu * dfmi::kWavesPerBlock);
-  const int64_t grid = bins_grid(t_ds->n_cu, per_cu, nrec * ((nseg + G - 1) / G));
+  const int64_t grid = bins_grid(t_ds->n_cu, per_cu, nrec * ((nseg + G - 1) / G), kEntryStagedSpw);
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(dfmi::kBlockThreads), lds, st, x, nrec, rec_stride, nseg, hop, L,
                      ndata, G, tab, qi, qi_ld, dc);
   HIPCHK(hipGetLastError());
@@ -1308,8 +1316,8 @@ int fused_seed_demod(const XT* x, int64_t nrec, int64_t nbuf, int R, int ndata, 
   int64_t bulk = slots - nrec;
   const int64_t need = (nseg + dfmi::kWavesPerBlock - 1) / dfmi::kWavesPerBlock;
   if (bulk > need) bulk = need;
-  if (t_tune.demod_spw > 0) {  // as bins_grid: later workgroups to the slots that free first
-    const int64_t per = (int64_t)dfmi::kWavesPerBlock * t_tune.demod_spw;
+  if (const int spw = demod_spw(kBinsSpw); spw > 0) {  // as bins_grid: later workgroups to the slots that free first
+    const int64_t per = (int64_t)dfmi::kWavesPerBlock * spw;
     if ((nseg + per - 1) / per > bulk) bulk = (nseg + per - 1) / per;
   }
   hipLaunchKernelGGL(kern, dim3((unsigned)(nrec + bulk)), dim3(dfmi::kBlockThreads), lds, st, x, nseg,
@@ -1503,7 +1511,7 @@ int nls_record_device(const XT* x, int64_t nrec, int64_t rec_stride, int64_t nbu
 }  // namespace
 
 namespace {
-// key -> (knob, allowed values or empty = any value >= 0)
+// key -> (knob, allowed values or empty = any value >= 0; demod_spw also -1)
 struct Knob {
   int Tuning::*v;
   std::vector<int> allowed;
@@ -2255,7 +2263,7 @@ int dfmi_probe_read(int64_t* out, int32_t n) {
   CallScope cs;
   if (int rc = ensure_init()) return rc;
   if (!t_ds->probe) return fail(DFMI_ERR_ARG, "probe not enabled on this device (dfmi_set_tuning(\"probe\", 1))");
-  if (n < 0 || n > 16 + 2 * dfmi::kProbeWaves || (n && !out)) return fail(DFMI_ERR_ARG, "bad probe read");
+  if (n < 0 || n > dfmi::kProbeWords || (n && !out)) return fail(DFMI_ERR_ARG, "bad probe read");
   HIPCHK(hipDeviceSynchronize());
   HIPCHK(hipMemcpy(out, t_ds->probe, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost));
   return DFMI_OK;
@@ -2284,7 +2292,7 @@ int dfmi_set_tuning(const char* key, int64_t value) {
     if (int rc = ensure_init()) return rc;
     if (value && !t_ds->probe) {
       void* p = nullptr;
-      const size_t pb = (16 + 2 * (size_t)dfmi::kProbeWaves) * sizeof(uint64_t);
+      const size_t pb = (size_t)dfmi::kProbeWords * sizeof(uint64_t);
       HIPCHK(hipMalloc(&p, pb));
       HIPCHK(hipMemset(p, 0, pb));
       t_ds->probe = (uint64_t*)p;
@@ -2298,7 +2306,8 @@ int dfmi_set_tuning(const char* key, int64_t value) {
   auto it = knobs().find(k);
   if (it == knobs().end()) return fail(DFMI_ERR_ARG, "unknown tuning key " + k);
   const Knob& kn = it->second;
-  if (value < 0 || value > (1 << 20)) return fail(DFMI_ERR_ARG, "tuning value out of range for " + k);
+  const int64_t lo = kn.v == &Tuning::demod_spw ? -1 : 0;  // demod_spw -1: each kernel's own
+  if (value < lo || value > (1 << 20)) return fail(DFMI_ERR_ARG, "tuning value out of range for " + k);
   if (!kn.allowed.empty()) {
     bool ok = false;
     for (int a : kn.allowed) ok = ok || (a == value);

@@ -536,7 +536,8 @@ int dfmi_wdfmi_fit(const double* x, int64_t nrec, int64_t rec_stride, int64_t nb
  * start. Results are unaffected (ekf_rot, ekf_pit*: rounding only). Keys: "demod_kernel" (1 phase bins in LDS where they
  * apply [default], 0 cycle-aligned fold), "lm_general" (1 = two-pass general LM path
  * for every ndata), "demod_spw" (segments per wave the bin grid is sized for; 0 =
- * persistent), "demod_wide" (1 [default]: component-major QI through the many-harmonic
+ * persistent, -1 [default] each kernel's own: 1 for the bin kernels, 2 for the frame and hop
+ * kernels), "demod_wide" (1 [default]: component-major QI through the many-harmonic
  * kernel demod_wide_kernel from "demod_wide_from" (13) harmonics or below "demod_wide_rmax"
  * (2000) samples per segment — the record pipeline then leaves its fused row layout; 0: the
  * bin / fold kernels; 2: demod_wide_kernel wherever its geometry applies; QI within ~1e-14
