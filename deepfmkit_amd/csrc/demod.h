@@ -24,7 +24,7 @@
 //
 // Sample type: the kernels that read samples are templates over XT (SampleT below), double,
 // float or int16_t; the loads widen in registers and nothing after the load depends on XT. The
-// bin, many-harmonic and seed kernels exist for all three; demod_fold_kernel and
+// bin, many-harmonic, seed and block kernels exist for all three; demod_fold_kernel and
 // demod_direct_kernel read doubles only (the host widens another type into a workspace for them).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -1688,6 +1688,192 @@ __global__ __launch_bounds__(kBlockThreads) void demod_direct_kernel(
   for (int64_t s = (int64_t)blockIdx.x * kWavesPerBlock + wave; s < nseg;
        s += (int64_t)gridDim.x * kWavesPerBlock) {
     direct_segment(x + s * seg_stride, R, ndata, w0, lane, qi, qi_ld, s, dc);
+  }
+}
+
+// ---- Block demodulation: no integer period, no per-sample transcendental -------------------
+//
+// With ω_h = fl(h·w0) (the reference's own first rounding) and t = b·B + j, B = kBlkLen = 64,
+//     Σ_t x[t]·e^{iω_h t} = Σ_b ρ_{h,b}·P_{h,b},   P_{h,b} = Σ_{j<B} x[bB + j]·τ_{h,j},
+//     τ_{h,j} = e^{iω_h j},   ρ_{h,b} = e^{iω_h B b};
+// Q_h / I_h are the real / imaginary part over R, and dc is the "harmonic" ω = 0 (τ = ρ = 1), so
+// a segment has ndata + 1 complex outputs ("slots", slot 0 = dc, slot h = harmonic h).
+//
+// P = X·τ is a matrix product on v_mfma_f64_16x16x4_f64. One wave owns one segment at a time
+// (persistent grid-stride). A row tile is 16 consecutive blocks (rows) = kBlkTile = 1024 samples;
+// a column tile is 8 slots: columns 0..7 their cos parts, columns 8..15 their sin parts, so
+// nt = ceil((ndata + 1) / 8) = ceil((2·ndata + 1) / 16) column tiles. Lane l = 16·k + i feeds row
+// i, and at MFMA step s < 16 its k-slice is sample j = 16·k + s of the row: the lane's 16 A
+// operands are the contiguous run x[(16·rt + i)·64 + 16·k ..+15], and its 16 B operands per
+// column tile are τ[column l % 16][16·(l / 16) + s], which the host lays out as
+// [tile][s][lane] — one coalesced wave load per (tile, s). They stay in VGPRs for the whole
+// kernel up to two column tiles (NTMAX = 2: 64 VGPRs) and are staged once per workgroup in LDS
+// beyond (same layout, lane-contiguous: conflict-free reads), the A operands held in registers
+// across the column tiles.
+//
+// B = 64 always, not 128: a segment's MFMA work is padded to whole row tiles, and 1024-sample
+// tiles never pad more than 2048-sample ones; the padded rows (segments down to R < 64) cost MFMA
+// issue only, never a load.
+//
+// Samples reach the A operands through a wave-private LDS tile (16 rows of 64 doubles at a row
+// stride of kBlkRowLd = 66: the 16 rows of a k-group read 16-B pairs without bank conflicts):
+// the wave loads the tile's 1024 samples lane-contiguously — VEC samples per lane and load, 16 B
+// when x and seg_stride allow (VEC = 16 / sizeof(XT)), else one sample (VEC = 1), legal at the
+// sample type's own alignment whatever R, seg_stride and the base pointer are — widens them in
+// registers and writes doubles. Every load is guarded by the segment's end; what lies beyond is
+// zero in the tile. The next tile's loads (the next segment's first, at a segment's end) are in
+// flight across the MFMA steps of the current one.
+//
+// D[row 4·v + l / 16][column l % 16] sits in register v of lane l. After a row tile's 16 steps
+// the wave rotates by ρ, one complex multiply per (block, slot): the partner part comes from lane
+// l ^ 8, and the host table holds (cos, ∓sin) of ω_h·64·b per (row tile, column tile, v, lane) —
+// zero for blocks past the segment and slots past ndata — so that cos columns accumulate the real
+// and sin columns the imaginary part with the same two FMAs. The lane-partial sums are added over
+// the four k-groups at the segment's end, divided by R and stored component-major.
+constexpr int kBlkLen = 64, kBlkTile = 16 * kBlkLen, kBlkRowLd = kBlkLen + 2;
+
+template <typename XT, int VEC>
+struct BlkRaw {
+  typedef XT V __attribute__((ext_vector_type(VEC)));
+  V v[16 / VEC];
+};
+template <typename XT>
+struct BlkRaw<XT, 1> {
+  XT v[16];
+};
+
+// The 1024 samples from xs + t0 on, 16 per lane: load c holds samples (64·c + lane)·VEC ..+VEC-1.
+template <typename XT, int VEC>
+__device__ __forceinline__ void blocks_load(const XT* __restrict__ xs, int t0, int R, int lane, BlkRaw<XT, VEC>& raw) {
+#pragma unroll
+  for (int c = 0; c < 16 / VEC; ++c) {
+    const int t = t0 + (c * 64 + lane) * VEC;
+    if constexpr (VEC == 1) {
+      raw.v[c] = t < R ? __builtin_nontemporal_load(xs + t) : (XT)0;
+    } else {
+      using V = typename BlkRaw<XT, VEC>::V;
+      V r = (V)(XT)0;
+      if (t + VEC <= R) {
+        r = __builtin_nontemporal_load(reinterpret_cast<const V*>(xs + t));
+      } else {
+#pragma unroll
+        for (int e = 0; e < VEC; ++e)
+          if (t + e < R) r[e] = xs[t + e];
+      }
+      raw.v[c] = r;
+    }
+  }
+}
+
+// Widened into the wave's LDS tile: sample e of the tile at row e / 64, column e % 64.
+template <typename XT, int VEC>
+__device__ __forceinline__ void blocks_stage(const BlkRaw<XT, VEC>& raw, int lane, double* __restrict__ tile) {
+#pragma unroll
+  for (int c = 0; c < 16 / VEC; ++c) {
+    const int e0 = (c * 64 + lane) * VEC;
+    double* p = tile + (e0 >> 6) * kBlkRowLd + (e0 & 63);
+    if constexpr (VEC == 1) {
+      p[0] = (double)raw.v[c];
+    } else {
+#pragma unroll
+      for (int e = 0; e < VEC; e += 2)
+        *reinterpret_cast<double2*>(p + e) = make_double2((double)raw.v[c][e], (double)raw.v[c][e + 1]);
+    }
+  }
+}
+
+// LDS writes and reads of one wave's own tile, ordered (no other wave touches it).
+__device__ __forceinline__ void blocks_wave_sync() {
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_wave_barrier();
+}
+
+// tau: [nt][16][64] doubles, rho: [ntile][nt][4][64] (cos, ∓sin) pairs (host: blocks_tables).
+// Dynamic LDS: NTMAX > 2: nt·1024 doubles of τ, then kWavesPerBlock tiles of 16·kBlkRowLd doubles.
+template <typename XT, int VEC, int NTMAX>
+__global__ __launch_bounds__(kBlockThreads) void demod_blocks_kernel(
+    const XT* __restrict__ x, int64_t nseg, int64_t seg_stride, int R, int ndata, int nt,
+    const double* __restrict__ tau, const double2* __restrict__ rho, double* __restrict__ qi, int64_t qi_ld,
+    double* __restrict__ dc) {
+  typedef double d4v __attribute__((ext_vector_type(4)));
+  constexpr bool TLDS = NTMAX > 2;
+  extern __shared__ double blk_lds[];
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  double* tile = blk_lds + (TLDS ? nt * 1024 : 0) + wave * (16 * kBlkRowLd);
+  double treg[TLDS ? 1 : 2][16];
+  if constexpr (TLDS) {
+    for (int i = threadIdx.x; i < nt * 1024; i += kBlockThreads) blk_lds[i] = tau[i];
+    __syncthreads();
+  } else {
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+      for (int s = 0; s < 16; ++s) treg[ct][s] = ct < nt ? tau[(ct * 16 + s) * 64 + lane] : 0.0;
+  }
+  const int ntile = (R + kBlkTile - 1) / kBlkTile;
+  const double* arow = tile + (lane & 15) * kBlkRowLd + (lane >> 4) * 16;
+  const int64_t s0 = (int64_t)blockIdx.x * kWavesPerBlock + wave, ds = (int64_t)gridDim.x * kWavesPerBlock;
+  BlkRaw<XT, VEC> raw;
+  if (s0 < nseg) blocks_load<XT, VEC>(x + s0 * seg_stride, 0, R, lane, raw);
+  for (int64_t sg = s0; sg < nseg; sg += ds) {
+    const XT* xs = x + sg * seg_stride;
+    double acc[NTMAX];
+#pragma unroll
+    for (int ct = 0; ct < NTMAX; ++ct) acc[ct] = 0.0;
+    for (int rt = 0; rt < ntile; ++rt) {
+      blocks_wave_sync();  // the previous tile's operand reads are done
+      blocks_stage<XT, VEC>(raw, lane, tile);
+      if (rt + 1 < ntile) blocks_load<XT, VEC>(xs, (rt + 1) * kBlkTile, R, lane, raw);
+      else if (sg + ds < nseg) blocks_load<XT, VEC>(x + (sg + ds) * seg_stride, 0, R, lane, raw);
+      blocks_wave_sync();
+      double a[16];
+#pragma unroll
+      for (int s = 0; s < 16; s += 2) {
+        const double2 v = *reinterpret_cast<const double2*>(arow + s);
+        a[s] = v.x;
+        a[s + 1] = v.y;
+      }
+      const double2* rp = rho + (int64_t)rt * nt * 256 + lane;
+#pragma unroll
+      for (int ct = 0; ct < NTMAX; ++ct) {
+        if (ct < nt) {
+          d4v d = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+          for (int s = 0; s < 16; ++s) {
+            double b;
+            if constexpr (TLDS) b = blk_lds[(ct * 16 + s) * 64 + lane];
+            else b = treg[ct][s];
+            d = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s], b, d, 0, 0, 0);
+          }
+#pragma unroll
+          for (int v = 0; v < 4; ++v) {
+            const double2 r = rp[(ct * 4 + v) * 64];
+            const double other = __shfl_xor(d[v], 8);
+            acc[ct] = fma(r.x, d[v], acc[ct]);
+            acc[ct] = fma(r.y, other, acc[ct]);
+          }
+        }
+      }
+    }
+    const int col = lane & 15;
+#pragma unroll
+    for (int ct = 0; ct < NTMAX; ++ct) {
+      if (ct < nt) {
+        double v = acc[ct];
+        v += __shfl_xor(v, 16);
+        v += __shfl_xor(v, 32);
+        v /= (double)R;
+        const int slot = ct * 8 + (col & 7);
+        if (lane < 16 && slot <= ndata) {
+          if (slot == 0) {
+            if (col == 0) dc[sg] = v;
+          } else {
+            qi[(int64_t)(col < 8 ? slot - 1 : ndata + slot - 1) * qi_ld + sg] = v;
+          }
+        }
+      }
+    }
   }
 }
 

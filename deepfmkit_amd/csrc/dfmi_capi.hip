@@ -100,6 +100,7 @@ struct Tuning {
   int demod_hop = 1;        // overlapped segments (dfmi_*_hop): demod_hop_kernel where hop_native() holds (0: the planar
                             // kernels in place at seg_stride = hop, A/B)
   int demod_hop_span = 0;   // demod_hop_kernel: output segments per span (0: the host's choice, hop_span)
+  int demod_blocks = 1;     // no integer period: demod_blocks_kernel (0: demod_direct_kernel's per-sample sincos, A/B)
   int demod_wide_dbg = 0;   // diagnostics: demod_wide_kernel without its contraction (1) / stores (2)
   int demod_wide_k = 0;     // demod_wide_kernel segments per wave (KSEG): 0 = 8; 2 / 4 / 8 (A/B)
   int ekf_row = 1;       // EKF: ekf_row_kernel (4 channels per wave) up to ekf_row x 4 x 4 x CUs channels
@@ -199,6 +200,7 @@ struct DeviceState {
   uint64_t ws_clock = 0;
   std::map<std::tuple<int, int, uint64_t>, DevBuf> basis;            // (L, ndata, w0 bits); (L, -(8 ndata + no), w0 bits): wide
   std::map<std::tuple<int, uint64_t, uint64_t, uint64_t>, DevBuf> gridtab;  // (ndata, min, max, step)
+  std::map<std::tuple<uint64_t, int, int, int>, DevBuf> blocks;     // (w0 bits, ndata, R, B): demod_blocks_kernel's tables
   std::map<int64_t, DevBuf> pwplan;                                 // n -> numpy pairwise-sum plan
   std::map<int, DevBuf> lpsd_rk2;                                    // 0 -> the 1/k^2 table of lpsd_i0
   std::map<std::pair<const void*, int>, int> occupancy;              // (kernel, LDS bytes) -> blocks per CU
@@ -867,6 +869,92 @@ int widen_rows(const XT* x, int64_t nseg, int64_t stride, int R, hipStream_t st,
   return DFMI_OK;
 }
 
+// ---- block demodulation (demod.h demod_blocks_kernel): records without a usable integer period ----
+constexpr int kBlocksMaxTiles = 8;  // column tiles of 8 slots: ndata + 1 <= 64 (beyond: the direct kernel)
+
+bool blocks_applicable(int ndata) { return t_tune.demod_blocks && ndata + 1 <= 8 * kBlocksMaxTiles; }
+
+// The two tables of demod_blocks_kernel in one buffer, in the kernel's operand layout (demod.h):
+//   τ [nt][16][64]:          column l % 16 of tile ct at sample j = 16·(l / 16) + s;
+//   ρ [ntile][nt][4][64][2]: (cos, ∓sin) of ω·64·b, block b = 16·rt + 4·v + l / 16 (the MFMA's D row
+//                            of register v), − for a cos column, + for a sin column.
+// Column c of tile ct: slot 8·ct + c % 8 (0 = dc with ω = 0, h = harmonic h with ω = fl(h·w0)), its
+// cos part for c < 8 and its sin part otherwise; zero for slots past ndata and blocks past the
+// segment. The angles are formed in long double (ω·j and ω·64·b: a 53-bit by 12-bit product is
+// exact there up to its last bit) and every entry is rounded once to double.
+int blocks_tables(int R, int ndata, double w0, const double** tau, const double2** rho) {
+  const int nt = (ndata + 8) / 8;
+  const int nblk = (R + dfmi::kBlkLen - 1) / dfmi::kBlkLen, ntile = (R + dfmi::kBlkTile - 1) / dfmi::kBlkTile;
+  const DevBuf* b;
+  if (int rc = cached_upload(t_ds->blocks, std::make_tuple(bits(w0), ndata, R, dfmi::kBlkLen), [&](int64_t*) {
+        std::vector<double> h((size_t)nt * 1024 + (size_t)ntile * nt * 512, 0.0);
+        double* hr = h.data() + (size_t)nt * 1024;
+        for (int ct = 0; ct < nt; ++ct)
+          for (int l = 0; l < 64; ++l) {
+            const int c = l % 16, slot = 8 * ct + c % 8;
+            if (slot > ndata) continue;
+            const long double w = slot ? (long double)((double)slot * w0) : 0.0L;
+            for (int s = 0; s < 16; ++s) {
+              const long double ang = w * (long double)(16 * (l / 16) + s);
+              h[((size_t)ct * 16 + s) * 64 + l] = (double)(c < 8 ? cosl(ang) : sinl(ang));
+            }
+            for (int rt = 0; rt < ntile; ++rt)
+              for (int v = 0; v < 4; ++v) {
+                const int blk = 16 * rt + 4 * v + l / 16;
+                if (blk >= nblk) continue;
+                const long double ang = w * (long double)(dfmi::kBlkLen * blk);
+                double* p = hr + ((((size_t)rt * nt + ct) * 4 + v) * 64 + l) * 2;
+                p[0] = (double)cosl(ang);
+                p[1] = (double)(c < 8 ? -sinl(ang) : sinl(ang));
+              }
+          }
+        return h;
+      }, &b))
+    return rc;
+  *tau = (const double*)b->p;
+  *rho = (const double2*)(*tau + (size_t)nt * 1024);
+  return DFMI_OK;
+}
+
+template <typename XT, int VEC, int NTMAX>
+int launch_blocks_t(const XT* x, int64_t nseg, int64_t stride, int R, int ndata, const double* tau, const double2* rho,
+                    double* qi, int64_t qi_ld, double* dc, hipStream_t st) {
+  const int nt = (ndata + 8) / 8;
+  auto kern = dfmi::demod_blocks_kernel<XT, VEC, NTMAX>;
+  const size_t lds = ((NTMAX > 2 ? (size_t)nt * 1024 : 0) + (size_t)dfmi::kWavesPerBlock * 16 * dfmi::kBlkRowLd) *
+                     sizeof(double);
+  int per_cu = 0;
+  if (int orc = occupancy(kern, dfmi::kBlockThreads, lds, &per_cu)) return orc;
+  if (per_cu < 1) per_cu = 1;
+  const int64_t grid = persistent_grid(t_ds->n_cu, per_cu, (nseg + dfmi::kWavesPerBlock - 1) / dfmi::kWavesPerBlock);
+  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(dfmi::kBlockThreads), lds, st, x, nseg, stride, R, ndata, nt, tau,
+                     rho, qi, qi_ld, dc);
+  HIPCHK(hipGetLastError());
+  g_last_demod = "demod_blocks_kernel<" + std::to_string(dfmi::kBlkLen) + "," + std::to_string(VEC) + "," +
+                 std::to_string(NTMAX) + ">" + xt_tag<XT>();
+  return DFMI_OK;
+}
+
+// blocks_applicable() holds. 16-B wave loads where every segment starts on a 16-B boundary, else
+// one sample per lane and load (any base pointer, any seg_stride).
+template <typename XT>
+int launch_blocks(const XT* x, int64_t nseg, int64_t stride, int R, int ndata, double w0, double* qi, int64_t qi_ld,
+                  double* dc, hipStream_t st) {
+  const double* tau = nullptr;
+  const double2* rho = nullptr;
+  if (int rc = blocks_tables(R, ndata, w0, &tau, &rho)) return rc;
+  constexpr int V = 16 / (int)sizeof(XT);
+  const bool vec = ((uintptr_t)x & 15) == 0 && (nseg == 1 || stride % V == 0);
+  const int nt = (ndata + 8) / 8;
+#define DFMI_BLOCKS(NT_)                                                                                  \
+  return vec ? launch_blocks_t<XT, V, NT_>(x, nseg, stride, R, ndata, tau, rho, qi, qi_ld, dc, st)        \
+             : launch_blocks_t<XT, 1, NT_>(x, nseg, stride, R, ndata, tau, rho, qi, qi_ld, dc, st)
+  if (nt <= 2) DFMI_BLOCKS(2);
+  if (nt <= 4) DFMI_BLOCKS(4);
+  DFMI_BLOCKS(8);
+#undef DFMI_BLOCKS
+}
+
 // Whether demod_device can write the row layout (dfmi_qi_row_stride) for this
 // input: only the bin-in-LDS kernel implements it.
 template <typename XT>
@@ -925,6 +1013,9 @@ int demod_device(const XT* x, int64_t nseg, int64_t stride, int R, int ndata, do
     }
   }
   if (rows) return fail(DFMI_ERR_UNSUPPORTED, "row layout needs the bin-in-LDS demodulation kernel");
+  // no integer period found (period = -1 still forces the direct kernel): the block kernel reads XT itself
+  if (period == 0 && L == 0 && blocks_applicable(ndata))
+    return launch_blocks(x, nseg, stride, R, ndata, w0, qi, qi_ld, dc, st);
   const double* xd = nullptr;
   int64_t sd = stride;
   if constexpr (std::is_same<XT, double>::value) xd = x;
@@ -1538,6 +1629,7 @@ const std::map<std::string, Knob>& knobs() {
       {"demod_frames", {&Tuning::demod_frames, {0, 1}}},
       {"demod_hop", {&Tuning::demod_hop, {0, 1}}},
       {"demod_hop_span", {&Tuning::demod_hop_span, {}}},
+      {"demod_blocks", {&Tuning::demod_blocks, {0, 1}}},
       {"demod_wide_dbg", {&Tuning::demod_wide_dbg, {0, 1, 2, 3, 4, 5, 6, 7}}},
       {"ekf_row", {&Tuning::ekf_row, {}}},
       {"ekf_rot", {&Tuning::ekf_rot, {0, 1}}},

@@ -95,7 +95,15 @@ void dfmi_lm_config_default(dfmi_lm_config* cfg);
  *                                        c >= ndata is I_{c-ndata+1} (sin)
  *   dc[s]                                output, mean(x) of the segment
  * period: samples per basis period L (L*w0 = 2*pi*integer), 0 = detect from
- * w0, -1 = force the direct (per-sample sincos) kernel. */
+ * w0, -1 = force the direct (per-sample sincos) kernel.
+ * period = 0 and no period L <= 1024 found (dfmi_detect_period = 0: an arbitrary f_samp / f_mod,
+ * or a slow modulation): demod_blocks_kernel, for up to 63 harmonics. It splits t = 64 b + j,
+ * forms the 64-sample block sums against a table e^{i w_h j} as fp64 matrix products and rotates
+ * each by a table entry e^{i w_h 64 b}, w_h = fl(h w0) as the reference rounds it: no periodicity
+ * assumed, no per-sample sin / cos, any R, seg_stride and base pointer (16-B loads where every
+ * segment starts on a 16-B boundary, single-sample loads otherwise). QI within a few 1e-15 of
+ * the direct kernel's at unit-scale signals. More harmonics, or the tuning key "demod_blocks" = 0,
+ * take the direct kernel. */
 int dfmi_demod(const double* x, int64_t nseg, int64_t seg_stride, int32_t R, int32_t ndata, double w0,
                int32_t period, double* qi, double* dc, int32_t mem, void* stream);
 
@@ -151,8 +159,9 @@ int dfmi_nls_record(const double* x, int64_t nrec, int64_t rec_stride, int64_t n
  * function gives on the same record widened to double (QI, dc, the six result columns and
  * fitok). With DFMI_MEM_HOST the record is staged and copied in its own type (a half or a
  * quarter of the bytes over the host link); it is never widened on the host.
- * The bin, fused seed + bin, many-harmonic and seed kernels read float and int16 themselves;
- * their vector-pair precondition is rows aligned to two samples at an even stride (4 B for
+ * The bin, fused seed + bin, many-harmonic, seed and block (no period found) kernels read float
+ * and int16 themselves; the period kernels' vector-pair precondition is rows aligned to two
+ * samples at an even stride (4 B for
  * int16, 8 B for float, 16 B for double). The branches left (the fold kernel: L < 128, odd L
  * or rows without pair alignment; the direct kernel) widen the rows into a device workspace
  * of 8 B per sample first and run the double kernel on it. dfmi_last_demod_kernel() says
@@ -545,6 +554,9 @@ int dfmi_wdfmi_fit(const double* x, int64_t nrec, int64_t rec_stride, int64_t nb
  * "demod_wide_half" (1 [default]: half-wave contraction at 2 ndata + 1 <= 32; same bits),
  * "demod_i16_int" (1 [default]: int16 records fold by integer accumulation in the bin kernels;
  * 0: the float kernels' fold; same bits),
+ * "demod_blocks" (1 [default]: a call whose period is detected and not found runs
+ * demod_blocks_kernel; 0: demod_direct_kernel, on a widened copy for float32 / int16; QI within
+ * rounding, ~1e-15 at unit scale),
  * "demod_wide_dbg" (diagnostics: bit 0 no contraction, bit 1 no stores, bit 2 segment-by-segment
  * fold — results invalid with bits 0 / 1), "ekf_row" (EKF row kernel up to ekf_row x 16 x CUs channels, 0 = lane
  * kernel only), "ekf_rot" (1 [default]: the row kernel takes sin / cos by rotation between
