@@ -34,7 +34,7 @@ SYMBOLS = ("dfmi_lm_config_default", "dfmi_demod", "dfmi_lm", "dfmi_nls_record",
            "dfmi_ekf_pit_trace", "dfmi_demod_typed", "dfmi_demod_rows_typed", "dfmi_nls_record_typed",
            "dfmi_fisher", "dfmi_lpsd_plan", "dfmi_lpsd", "dfmi_plnoise_design", "dfmi_plnoise",
            "dfmi_synth_asd_coloured", "dfmi_lcsd", "dfmi_demod_frames", "dfmi_nls_record_frames",
-           "dfmi_demod_hop", "dfmi_nls_record_hop")
+           "dfmi_demod_hop", "dfmi_nls_record_hop", "dfmi_residual")
 
 
 class DFMIError(RuntimeError):
@@ -247,6 +247,8 @@ def load():
         lib.dfmi_bessel_eval.restype = ctypes.c_int
         lib.dfmi_fisher.argtypes = [P, i64, i64, i32, P, dbl, P, P, P, P, i32, P]
         lib.dfmi_fisher.restype = ctypes.c_int
+        lib.dfmi_residual.argtypes = [P, i32, i64, i64, i32, dbl, i32, P, i64, P, P, P, P, P, i64, i32, P]
+        lib.dfmi_residual.restype = ctypes.c_int
         lib.dfmi_lpsd_plan.argtypes = [i64, dbl, dbl, dbl, i64, i64, i64, P, P, P, P, P, i64]
         lib.dfmi_lpsd_plan.restype = i64
         lib.dfmi_lpsd.argtypes = [P, i64, i64, i64, dbl, P, P, P, i64, i32, dbl, P, P, i32, P]

@@ -62,6 +62,7 @@ class DeepFitFramework:
         self.raws = {}
         self.fits = {}
         self.fits_df = {}
+        self._fit_source = {}  # fit label -> the raw label it was fitted from (residual)
         self.channr = None
         self.n = None
         self.t0 = None
@@ -276,7 +277,13 @@ class DeepFitFramework:
         (n_samples - R)//k + 1 points, fs = f_samp/k and its time axis on that rate, R unchanged
         and the new attribute hop; phi_sim_downsamp is the R-sample mean at each hop. Overlapped
         points share samples: neighbouring points are correlated (a spectrum of the series is
-        that of an R-sample moving average sampled at f_samp/k)."""
+        that of an R-sample moving average sampled at f_samp/k).
+
+        residuals=True (method 'nls' only): the frame also carries res_rms, res_peak, res_peak_t
+        (rms and peak of each buffer's time-domain residual and the sample index of the peak
+        within the buffer, StandardNLSFitter.fit), after the error columns when both are asked
+        for; the DeepFitObject gets attributes of the same names. residual(fit_label) returns
+        the residual record itself."""
         _fitters.mark("fit")
         fitter_map = _fitters.FITTER_MAP
         if method not in fitter_map:
@@ -284,6 +291,8 @@ class DeepFitFramework:
             return
         if kwargs.get("errors") and method != "nls":
             raise ValueError(f"errors=True is available for method 'nls' only, got '{method}'")
+        if kwargs.get("residuals") and method != "nls":
+            raise ValueError(f"residuals=True is available for method 'nls' only, got '{method}'")
         hop = kwargs.get("hop")
         if hop is not None and method != "nls":
             raise ValueError(f"hop= is available for method 'nls' only, got '{method}'")
@@ -353,10 +362,14 @@ class DeepFitFramework:
         if "m_err" in cols:
             for k in _fitters.ERR_COLUMNS + ["tau_err"]:
                 setattr(fit, k, cols[k])
+        if "res_rms" in cols:
+            for k in _fitters.RES_COLUMNS:
+                setattr(fit, k, cols[k])
         _fitters.mark("columns")
         fit.time = _time_axis(fit.ssq.shape[0], fit.fs)
         fit.label = fit_label
         self.fits[fit_label] = fit
+        self._fit_source[fit_label] = main_label
         _fitters.mark("fitobj")
         return fit
 
@@ -371,6 +384,8 @@ class DeepFitFramework:
         errors=True (method 'nls' only) as in fit(). Returns {label: DeepFitObject}."""
         if kwargs.get("errors") and method != "nls":
             raise ValueError(f"errors=True is available for method 'nls' only, got '{method}'")
+        if kwargs.get("residuals"):
+            raise ValueError("residuals=True is not available for fit_many: fit the channels one by one")
         raws = [self.raws[l] for l in labels]
         r0 = raws[0]
         if any(r.f_samp != r0.f_samp or r.f_mod != r0.f_mod or r.n_samples() != r0.n_samples() for r in raws):
@@ -411,6 +426,20 @@ class DeepFitFramework:
             df = df_all.iloc[i * nbuf:(i + 1) * nbuf].reset_index(drop=True)
             out[l] = self._finish(f"{l}_{method}", l, raw, method, df, n, R, fs, nbuf)  # fit()'s default label
         return out
+
+    def residual(self, fit_label):
+        """The (nbuf, R) float64 time-domain residual of the NLS fit `fit_label` over the record
+        it was fitted from, which must still be loaded (fitters.residual_record): a CUDA tensor
+        for a record on the device, numpy otherwise. Rows follow the fit's buffers (its hop)."""
+        fit = self.fits[fit_label]
+        raw = self.raws.get(self._fit_source.get(fit_label))
+        if raw is None or not hasattr(fit, "hop"):
+            raise KeyError(f"the record fit '{fit_label}' was fitted from is not loaded")
+        x = raw.samples()
+        if _fitters._is_device_tensor(x) and x.ndim == 1 and x.shape[0] > 1 and x.stride(0) != 1:
+            x = x.contiguous()  # a column of a frames block
+        params = np.stack([fit.amp, fit.m, fit.phi, fit.psi])
+        return _fitters.residual_record(x, raw.f_samp, raw.f_mod, fit.R, params, fit.dc, hop=fit.hop)
 
     # --- spectra (core.py:590-609) ------------------------------------------------
     def calc_lpsd(self, labels=None, which="phi"):

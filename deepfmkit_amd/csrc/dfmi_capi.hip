@@ -34,6 +34,7 @@
 #include "plnoise.h"
 #include "wdfmi.h"
 #include "lpsd.h"
+#include "residual.h"
 
 namespace dfmi {
 hipError_t lpsd_batch_launch(const double* x, int64_t nser, int64_t ser_stride, int64_t N, double fs,
@@ -2885,6 +2886,55 @@ int dfmi_fisher(const double* params, int64_t n, int64_t ld, int32_t ndata, cons
   if (ok) HIPCHK(hipMemcpyAsync(ok, dok, (size_t)n * 4, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   return DFMI_OK;
+}
+
+int dfmi_residual(const void* x, int32_t xtype, int64_t nseg, int64_t seg_stride, int32_t R, double w0,
+                  int32_t period, const double* params, int64_t ld, const double* dc, double* rss, double* peak,
+                  int32_t* ipeak, double* resid, int64_t resid_stride, int32_t mem, void* stream) {
+  CallScope cs(stream);
+  if (bad_xtype(xtype)) return fail(DFMI_ERR_ARG, "unknown sample type");
+  if (nseg < 0 || R < 1 || seg_stride < 1 || ld < nseg || period < -1)
+    return fail(DFMI_ERR_ARG, "bad residual geometry (nseg >= 0, R >= 1, seg_stride >= 1, ld >= nseg, period >= -1)");
+  if (R > INT32_MAX - 4096) return fail(DFMI_ERR_UNSUPPORTED, "residual: R too close to 2^31");
+  if (!rss && !peak && !ipeak && !resid) return fail(DFMI_ERR_ARG, "residual: one of rss, peak, ipeak, resid is required");
+  if (resid && resid_stride < R) return fail(DFMI_ERR_ARG, "resid_stride < R");
+  if (!dc || (nseg > 0 && (!x || !params))) return fail(DFMI_ERR_ARG, "null pointer");
+  int rc = ensure_init();
+  if (rc) return rc;
+  if (nseg == 0) return DFMI_OK;
+  // the table's period: a multiple of L of at least 8 samples (a lane's 16-B load of int16) is one too
+  int L = period;
+  if (L == 0) L = detect_period_impl(w0, R, 1);
+  if (L < 0) L = 0;
+  if (L > 0 && L < 8) L *= (8 + L - 1) / L;
+  if (L > dfmi::kResMaxL) L = 0;
+  hipStream_t st = (hipStream_t)stream;
+  Staging sg(mem, st);
+  const size_t xsz = xtype == DFMI_F64 ? 8 : xtype == DFMI_F32 ? 4 : 2;
+  const char* dx;
+  const double *dp, *dd;
+  double *drss = nullptr, *dpeak = nullptr, *dres = nullptr;
+  int32_t* dip = nullptr;
+  int64_t dres_stride = resid_stride;
+  if ((rc = sg.in("r_x", (const char*)x, (size_t)((nseg - 1) * seg_stride + R) * xsz, &dx))) return rc;
+  if ((rc = sg.in("r_p", params, (size_t)(3 * ld + nseg) * 8, &dp))) return rc;
+  if ((rc = sg.in("r_dc", dc, (size_t)nseg * 8, &dd))) return rc;
+  if (rss && (rc = sg.out("r_rss", rss, (size_t)nseg * 8, &drss))) return rc;
+  if (peak && (rc = sg.out("r_peak", peak, (size_t)nseg * 8, &dpeak))) return rc;
+  if (ipeak && (rc = sg.out("r_ipeak", ipeak, (size_t)nseg * 4, &dip))) return rc;
+  if (resid) {
+    dres = resid;
+    if (sg.host) {  // staged by hand: rows packed at an even stride, copied back row by row (a strided 2-D copy)
+      dres_stride = R + (R & 1);
+      if ((rc = workspace("r_resid", (size_t)nseg * dres_stride * 8, (void**)&dres))) return rc;
+    }
+  }
+  HIPCHK(dfmi::residual_launch(dx, xtype, nseg, seg_stride, R, w0, L, dp, ld, dd, drss, dpeak, dip, dres, dres_stride,
+                               t_ds->n_cu, st));
+  if (resid && sg.host)
+    HIPCHK(hipMemcpy2DAsync(resid, (size_t)resid_stride * 8, dres, (size_t)dres_stride * 8, (size_t)R * 8, (size_t)nseg,
+                            hipMemcpyDeviceToHost, st));
+  return sg.finish();
 }
 
 }  // extern "C"

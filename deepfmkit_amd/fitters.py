@@ -36,6 +36,7 @@ log = logging.getLogger(__name__)
 
 COLUMNS = ["amp", "m", "phi", "psi", "dc", "ssq", "fitok"]
 ERR_COLUMNS = ["amp_err", "m_err", "phi_err", "psi_err"]  # fit(errors=True): appended after fitok
+RES_COLUMNS = ["res_rms", "res_peak", "res_peak_t"]  # fit(residuals=True): appended after fitok / the errors
 
 # Facade timing marks (scripts/profile_facade.py sets a list here): (label, perf_counter())
 # appended at each stage of DeepFitFramework.fit's NLS path; None = off (one test per mark).
@@ -115,8 +116,94 @@ def _segment_errors(lib, out, nseg, ndata, mem, stream):
     return sig
 
 
+def _residual_calls(nrec, rec_stride, nbuf, seg_stride):
+    """(first segment, segments, sample offset) of the dfmi_residual calls that cover nrec records
+    of nbuf segments: one call where the segments of all records lie at one stride, else one per
+    record."""
+    if nrec <= 1 or rec_stride == nbuf * seg_stride:
+        return [(0, nrec * nbuf, 0)]
+    return [(r * nbuf, nbuf, r * rec_stride) for r in range(nrec)]
+
+
+def _segment_residuals(lib, x, nrec, rec_stride, nbuf, R, seg_stride, w0, out, mem, stream):
+    """The (3, nseg) block [rms, peak, ipeak] of the time-domain residual of the fits in `out`
+    (nls_records' result block, read in place: rows 0-3 the parameters, row 4 dc, leading
+    dimension nseg) over the samples x (dfmi_residual, include/dfmi.h): rms = sqrt(rss/R). For a
+    device block everything is formed on `stream`, behind the record call."""
+    nseg = nrec * nbuf
+    item = x.element_size() if mem == _lib.DFMI_MEM_DEVICE else x.itemsize
+    if mem == _lib.DFMI_MEM_DEVICE:
+        import torch
+        res = torch.empty((3, nseg), dtype=torch.float64, device=out.device)
+        ip = torch.empty(nseg, dtype=torch.int32, device=out.device)
+    else:
+        res = np.empty((3, nseg))
+        ip = np.empty(nseg, dtype=np.int32)
+    base, rb, ib = _lib.ptr(out), _lib.ptr(res), _lib.ptr(ip)
+    for s0, n, off in _residual_calls(nrec, rec_stride, nbuf, seg_stride):
+        rc = lib.dfmi_residual(_lib.ptr(x) + off * item, _xtype(x.dtype), n, seg_stride, R, w0, 0, base + s0 * 8, nseg,
+                               base + (4 * nseg + s0) * 8, rb + s0 * 8, rb + (nseg + s0) * 8, ib + s0 * 4, None, 0,
+                               mem, stream)
+        _lib.check(rc, "dfmi_residual")
+    if mem == _lib.DFMI_MEM_DEVICE:
+        res[0].div_(R).sqrt_()
+    else:
+        np.sqrt(res[0] / R, out=res[0])
+    res[2] = ip
+    return res
+
+
+def residual_record(x, f_samp, f_mod, R, params, dc, hop=None):
+    """The time-domain residual r(t) = x(t) - k - amp cos(phi + m cos(w0 t + psi)) of fitted
+    segments, (nseg, R) float64 (dfmi_residual's resid; k makes each row's mean zero).
+
+    x: a 1-D record (segment s at samples [s*hop, s*hop + R), hop = R unless given) or a 2-D
+    (nseg, >= R) block of rows, float64, float32 or int16, numpy or a CUDA tensor; params
+    (4, nseg): amp, m, phi, psi; dc (nseg,): each segment's mean, as the fit returns it. A torch
+    tensor on x's device for a device x, numpy otherwise."""
+    lib = _lib.load()
+    dev = _is_device_tensor(x)
+    if not dev:
+        x = np.ascontiguousarray(_host_samples(x))
+    xtype = _xtype(x.dtype)
+    if xtype is None or (dev and x.stride(-1) != 1):
+        raise ValueError("records must be contiguous float64, float32 or int16 rows")
+    to_host = lambda v: v.cpu().numpy() if hasattr(v, "cpu") else np.asarray(v)
+    if dev:
+        import torch
+        on = lambda v: (v if hasattr(v, "cpu") else torch.from_numpy(np.ascontiguousarray(v, dtype=np.float64))).to(
+            device=x.device, dtype=torch.float64).contiguous()
+    else:
+        on = lambda v: np.ascontiguousarray(to_host(v), dtype=np.float64)
+    p, d = on(params), on(dc).reshape(-1)
+    if p.ndim != 2 or p.shape[0] != 4 or d.shape[0] != p.shape[1]:
+        raise ValueError("params must be (4, nseg) and dc (nseg,)")
+    nseg = int(p.shape[1])
+    if x.ndim == 2:
+        stride = int(x.stride(0)) if dev else int(x.strides[0] // x.itemsize)
+        if int(x.shape[0]) != nseg or int(x.shape[1]) < R:
+            raise ValueError("a 2-D x must be (nseg, >= R)")
+        stride = max(stride, 1)
+    else:
+        stride = R if hop is None else int(hop)
+        if stride < 1 or int(x.shape[0]) < (nseg - 1) * stride + R:
+            raise ValueError("record shorter than (nseg-1)*hop + R, or hop < 1")
+    w0 = w0_of(f_mod, f_samp)
+    if dev:
+        out = torch.empty((nseg, R), dtype=torch.float64, device=x.device)
+        with _on_device(x):
+            rc = lib.dfmi_residual(x.data_ptr(), xtype, nseg, stride, R, w0, 0, p.data_ptr(), nseg, d.data_ptr(), None,
+                                   None, None, out.data_ptr(), R, _lib.DFMI_MEM_DEVICE, _torch_stream(x.device))
+    else:
+        out = np.empty((nseg, R))
+        rc = lib.dfmi_residual(_lib.ptr(x), xtype, nseg, stride, R, w0, 0, _lib.ptr(p), nseg, _lib.ptr(d), None, None,
+                               None, _lib.ptr(out), R, _lib.DFMI_MEM_HOST, None)
+    _lib.check(rc, "dfmi_residual")
+    return out
+
+
 def nls_records(records, f_samp, f_mod, R, nbuf, ndata=10, init_guess=(1.6, 6.0, 0.0, 0.0), parallel=True,
-                n_cores=None, errors=False, hop=None):
+                n_cores=None, errors=False, hop=None, residuals=False):
     """Run the StandardNLSFitter pipeline on one or more equal-length records in ONE
     GPU call (config 3: several channels as one batch).
 
@@ -136,7 +223,9 @@ def nls_records(records, f_samp, f_mod, R, nbuf, ndata=10, init_guess=(1.6, 6.0,
     amplitude is in counts too. init_guess: (4,) shared or (nrec, 4). Returns (cols (6, nrec*nbuf) in the order amp, m, phi, psi, dc, ssq; fitok
     (nrec*nbuf,)), as numpy arrays for host input and as CUDA tensors for device input.
     errors=True: a third value, the (4, nrec*nbuf) standard errors of amp, m, phi, psi
-    (_segment_errors; NaN where J^T J at the fitted point has no inverse); ndata >= 3."""
+    (_segment_errors; NaN where J^T J at the fitted point has no inverse); ndata >= 3.
+    residuals=True: one more value (the last), the (3, nrec*nbuf) block [rms, peak, ipeak] of each
+    segment's time-domain residual (_segment_residuals: one more pass over the samples)."""
     if errors:
         _check_errors_ndata(ndata)
     lib = _lib.load()
@@ -196,11 +285,15 @@ def nls_records(records, f_samp, f_mod, R, nbuf, ndata=10, init_guess=(1.6, 6.0,
                                                _torch_stream(x.device))
         _lib.check(rc, "dfmi_nls_record")
         mark("enqueue")
+        more = ()
         if errors:
             with _on_device(x):
-                sig = _segment_errors(lib, out, nseg, ndata, _lib.DFMI_MEM_DEVICE, _torch_stream(x.device))
-            return out, ok, sig
-        return out, ok
+                more = (_segment_errors(lib, out, nseg, ndata, _lib.DFMI_MEM_DEVICE, _torch_stream(x.device)),)
+        if residuals:
+            with _on_device(x):
+                more += (_segment_residuals(lib, x, nrec, rec_stride, nbuf, R, R if hop is None else hop, w0, out,
+                                            _lib.DFMI_MEM_DEVICE, _torch_stream(x.device)),)
+        return (out, ok) + more
     out = np.empty((6, nseg))
     ok = np.empty(nseg, dtype=np.int32)
     if hop is not None:
@@ -216,20 +309,30 @@ def nls_records(records, f_samp, f_mod, R, nbuf, ndata=10, init_guess=(1.6, 6.0,
                                  1 if parallel else 0, max(nchunk, 1), cfg, _lib.ptr(out), _lib.ptr(ok),
                                  _lib.DFMI_MEM_HOST, None)
     _lib.check(rc, "dfmi_nls_record")
+    more = ()
     if errors:
-        return out, ok, _segment_errors(lib, out, nseg, ndata, _lib.DFMI_MEM_HOST, None)
-    return out, ok
+        more = (_segment_errors(lib, out, nseg, ndata, _lib.DFMI_MEM_HOST, None),)
+    if residuals:
+        more += (_segment_residuals(lib, x, nrec, rec_stride, nbuf, R, R if hop is None else hop, w0, out,
+                                    _lib.DFMI_MEM_HOST, None),)
+    return (out, ok) + more
+
+
+def _no_residuals(residuals, what):
+    if residuals:
+        raise ValueError(f"residuals=True is not available for {what}")
 
 
 def nls_frames(frames, f_samp, f_mod, R, nbuf, ndata=10, init_guess=(1.6, 6.0, 0.0, 0.0), parallel=True,
-               n_cores=None, errors=False):
+               n_cores=None, errors=False, residuals=False):
     """nls_records on the nch records that frame-interleaved samples hold, with no transposed
     copy: frames is a 2-D (N >= nbuf*R, nch) numpy array or CUDA tensor with stride(1) == 1
     (row t = sample t of every channel, as a digitiser delivers them; stride(0) > nch: padded
     frames) of float64, float32 or int16. Returns what nls_records returns for the planar records
     frames[:, c], channel by channel (segment c*nbuf + b), bit for bit. int16 frames of 2, 4 or
     8 channels are folded as they lie (dfmi_nls_record_frames, include/dfmi.h); anything else
-    is de-interleaved on the device first."""
+    is de-interleaved on the device first. residuals=True is refused (ValueError)."""
+    _no_residuals(residuals, "frame-interleaved records (nls_frames)")
     if errors:
         _check_errors_ndata(ndata)
     dev = _is_device_tensor(frames)
@@ -444,15 +547,20 @@ def frame_from(cols, fitok, tau_div=NO_TAU):
     return df
 
 
-def frame_with_errors(cols, fitok, sig):
-    """frame_from's frame with the float64 columns amp_err, m_err, phi_err, psi_err appended
-    after fitok (fit(errors=True)); the seven base columns are frame_from's own arrays."""
+def frame_with_errors(cols, fitok, sig=None, res=None):
+    """frame_from's frame with the float64 columns amp_err, m_err, phi_err, psi_err (sig,
+    fit(errors=True)) and res_rms, res_peak, res_peak_t (res, fit(residuals=True)) appended after
+    fitok, in that order; the seven base columns are frame_from's own arrays."""
     df = frame_from(cols, fitok)  # kept alive: frame_arrays answers for a living frame only
-    base = frame_arrays(df)[0]
-    if hasattr(sig, "cpu"):
-        sig = sig.cpu().numpy()
-    sig = np.ascontiguousarray(sig, dtype=np.float64)
-    return pd.DataFrame({**base, **{k: sig[i] for i, k in enumerate(ERR_COLUMNS)}}, copy=False)
+    more = dict(frame_arrays(df)[0])
+    for block, names in ((sig, ERR_COLUMNS), (res, RES_COLUMNS)):
+        if block is None:
+            continue
+        if hasattr(block, "cpu"):
+            block = block.cpu().numpy()
+        block = np.ascontiguousarray(block, dtype=np.float64)
+        more.update({k: block[i] for i, k in enumerate(names)})
+    return pd.DataFrame(more, copy=False)
 
 
 class BaseFitter(ABC):
@@ -483,7 +591,11 @@ class StandardNLSFitter(BaseFitter):
     standard errors sqrt(diag(ssq/(2 ndata - 4) (J^T J)^-1)) at each buffer's fitted parameters
     (dfmi_fisher on the device, behind the fit; needs ndata >= 3).
     hop=k (samples, k < R): a sliding-window readout, one point per k samples from windows of R
-    (nls_records' hop; neighbouring points are correlated); not with devices=."""
+    (nls_records' hop; neighbouring points are correlated); not with devices=.
+    residuals=True appends the float64 columns res_rms, res_peak, res_peak_t (after the error
+    columns when both are asked for): rms and peak of each buffer's time-domain residual and the
+    sample index of the peak within the buffer (dfmi_residual on the record's side, behind the
+    fit); not with devices= and not for a column of a frames block."""
 
     def fit(self, main_raw, **kwargs) -> pd.DataFrame:
         n = self.config["n"]
@@ -493,8 +605,11 @@ class StandardNLSFitter(BaseFitter):
         init_m = kwargs.get("init_m", 6.0)
         init_psi = kwargs.get("init_psi", 0.0)
         errors = bool(kwargs.get("errors", False))
+        residuals = bool(kwargs.get("residuals", False))
         if errors:
             _check_errors_ndata(ndata)
+        if residuals:
+            _no_residuals(kwargs.get("devices") is not None, "sharded records (devices=)")
         R, _, nbuf = _calculate_fit_params(main_raw, n)
         if nbuf == 0:
             return pd.DataFrame()
@@ -509,8 +624,11 @@ class StandardNLSFitter(BaseFitter):
                 xs = xs.contiguous()  # a column of a frames block
             res = nls_records(xs.reshape(1, N), main_raw.f_samp, main_raw.f_mod, R, None, ndata,
                               (init_a, init_m, 0.0, init_psi), parallel=parallel,
-                              n_cores=kwargs.get("n_cores") if parallel else None, errors=errors, hop=int(hop))
-            return frame_with_errors(*res) if errors else frame_from(*res, tau_divisor(main_raw))
+                              n_cores=kwargs.get("n_cores") if parallel else None, errors=errors, hop=int(hop),
+                              residuals=residuals)
+            if errors or residuals:
+                return frame_with_errors(res[0], res[1], res[2] if errors else None, res[-1] if residuals else None)
+            return frame_from(*res, tau_divisor(main_raw))
         if N % R != 0:
             # the reference reshapes the whole column with reshape(-1, R) (fitters.py:375, 412)
             raise ValueError(f"cannot reshape array of size {N} into shape ({R})")
@@ -530,6 +648,11 @@ class StandardNLSFitter(BaseFitter):
                 one, fit_records = x[:, None], nls_frames
             else:
                 one = x.reshape(1, N)
+        if residuals:  # devices is None; a frames column is refused by nls_frames
+            res = fit_records(one, main_raw.f_samp, main_raw.f_mod, R, nbuf, ndata, (init_a, init_m, 0.0, init_psi),
+                              parallel=parallel, n_cores=kwargs.get("n_cores") if parallel else None, errors=errors,
+                              residuals=True)
+            return frame_with_errors(res[0], res[1], res[2] if errors else None, res[-1])
         if errors:
             g = (init_a, init_m, 0.0, init_psi)
             if devices is not None:

@@ -37,6 +37,7 @@
  *                    trial, the input side of workers.run_efficiency_trial batches
  *   dfmi_wdfmi_fit   WDFMI_NLSFitter / WDFMI_OrthogonalFitter / WDFMI_SequentialFitter /
  *                    HWDFMI_Fitter .fit (fitters.py:481-891)
+ *   dfmi_residual    the time-domain residual of the fitted model per segment: rss, peak, the record
  *   dfmi_fisher      the J^T J of coeffs (fit.py:68-150) and its inverse at caller points:
  *                    calculate_crlb_for_m / calculate_m_precision (helpers.py:16-45, 98-132),
  *                    and the per-segment standard errors of a fit (no reference counterpart)
@@ -444,6 +445,34 @@ int dfmi_bessel_eval(const double* x, int64_t nx, int32_t nmax, int32_t method, 
  * ndata: any value dfmi_lm's general path takes (ndata > 0). n == 0 launches nothing. */
 int dfmi_fisher(const double* params, int64_t n, int64_t ld, int32_t ndata, const double* var, double var_mul,
                 double* jtj, double* cov, double* sigma, int32_t* ok, int32_t mem, void* stream);
+
+/* Time-domain residual of the fitted model, per segment. For segment s
+ * of R samples x[t] at local time t = 0..R-1, with fit results (amp, m, phi, psi) and dc = mean(x):
+ *     ac(t) = amp cos(phi + m cos(w0 t + psi)),  k = dc - (1/R) sum_t ac(t),  r(t) = x(t) - k - ac(t)
+ * (k is the least-squares offset given the four parameters: r has zero mean for any R; the
+ * normalisation of the parameters does not matter, negative amp or m included).
+ *   x, xtype, seg_stride   as in dfmi_demod_typed (DFMI_F64, DFMI_F32, DFMI_I16; strides in
+ *                          elements), but any seg_stride >= 1: overlapped segments are
+ *                          seg_stride = hop. Any alignment; 16-byte aligned rows are read 16 bytes
+ *                          per lane
+ *   params[i*ld + s], i < 4, ld >= nseg   amp, m, phi, psi: dfmi_lm's params, or rows 0-3 of
+ *                          dfmi_nls_record's out read in place (ld = nrec*nbuf, dc = out + 4*ld)
+ *   dc[s]                  mean(x) of segment s (required)
+ *   period                 dfmi_demod's: 0 = detect, > 0 = the basis period L in samples, -1 =
+ *                          none. Up to L = 1024 the model is tabulated once per segment; otherwise
+ *                          it is evaluated per sample
+ *   rss[s]                 sum_t r(t)^2
+ *   peak[s], ipeak[s]      max_t |r(t)| and its t (the smallest t on an exact tie)
+ *   resid[s*resid_stride + t], resid_stride >= R   r(t)
+ * Each of rss, peak, ipeak, resid may be NULL (not written), but not all four. A non-finite
+ * parameter or dc gives rss = peak = NaN, ipeak = -1 and a NaN residual row; a non-finite sample
+ * propagates as the arithmetic has it (a NaN rss gives peak = NaN, ipeak = -1). DFMI_ERR_ARG: an
+ * unknown xtype, R < 1, seg_stride < 1, ld < nseg, resid_stride < R with resid, dc NULL, period <
+ * -1. nseg == 0 launches nothing. With a tabulated model the result does not depend on the sample
+ * type or on alignment: a float or int16 record gives the bits of the widened double record. */
+int dfmi_residual(const void* x, int32_t xtype, int64_t nseg, int64_t seg_stride, int32_t R, double w0,
+                  int32_t period, const double* params, int64_t ld, const double* dc, double* rss, double* peak,
+                  int32_t* ipeak, double* resid, int64_t resid_stride, int32_t mem, void* stream);
 
 /* ---- Log-frequency spectral density (LPSD) of a series ----
  * The one-sided power spectral density at logarithmically spaced frequencies, one DFT bin per
