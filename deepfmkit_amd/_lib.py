@@ -34,7 +34,24 @@ SYMBOLS = ("dfmi_lm_config_default", "dfmi_demod", "dfmi_lm", "dfmi_nls_record",
            "dfmi_ekf_pit_trace", "dfmi_demod_typed", "dfmi_demod_rows_typed", "dfmi_nls_record_typed",
            "dfmi_fisher", "dfmi_lpsd_plan", "dfmi_lpsd", "dfmi_plnoise_design", "dfmi_plnoise",
            "dfmi_synth_asd_coloured", "dfmi_lcsd", "dfmi_demod_frames", "dfmi_nls_record_frames",
-           "dfmi_demod_hop", "dfmi_nls_record_hop", "dfmi_residual")
+           "dfmi_demod_hop", "dfmi_nls_record_hop", "dfmi_residual", "dfmi_demod_window",
+           "dfmi_nls_record_window")
+
+# cosine-sum windows by name: w[t] = sum_m a_m cos(2 pi m t / R) (dfmi_demod_window)
+WINDOWS = {"hann": (0.5, -0.5), "hamming": (0.54, -0.46), "blackman": (0.42, -0.5, 0.08),
+           "blackmanharris": (0.35875, -0.48829, 0.14128, -0.01168)}
+
+
+def window_coefficients(window):
+    """The float64 coefficient array of window=: a name from WINDOWS or a sequence of 1-4 numbers."""
+    if isinstance(window, str):
+        if window not in WINDOWS:
+            raise ValueError(f"unknown window '{window}': one of {sorted(WINDOWS)} or 1-4 coefficients")
+        window = WINDOWS[window]
+    a = np.ascontiguousarray(window, dtype=np.float64).reshape(-1)
+    if not 1 <= a.size <= 4:
+        raise ValueError(f"a window has 1 to 4 cosine-sum coefficients, got {a.size}")
+    return a
 
 
 class DFMIError(RuntimeError):
@@ -223,6 +240,13 @@ def load():
         lib.dfmi_demod_hop.restype = ctypes.c_int
         lib.dfmi_nls_record_hop.argtypes = [P, i32, i64, i64, i64, i32, i32] + lib.dfmi_nls_record.argtypes[5:]
         lib.dfmi_nls_record_hop.restype = ctypes.c_int
+        # windowed: the typed / hop arguments with (wcoef, nwcoef) after period
+        lib.dfmi_demod_window.argtypes = (lib.dfmi_demod_typed.argtypes[:8] + [P, i32]
+                                          + lib.dfmi_demod_typed.argtypes[8:])
+        lib.dfmi_demod_window.restype = ctypes.c_int
+        lib.dfmi_nls_record_window.argtypes = (lib.dfmi_nls_record_hop.argtypes[:10] + [P, i32]
+                                               + lib.dfmi_nls_record_hop.argtypes[10:])
+        lib.dfmi_nls_record_window.restype = ctypes.c_int
         lib.dfmi_ekf.argtypes = [P, i64, i64, i64, P, P, P, P, dbl, dbl, i32, i64, P, i32, P]
         lib.dfmi_ekf.restype = ctypes.c_int
         lib.dfmi_ekf_fit.argtypes = [P, i64, i64, i64, P, P, P, P, dbl, dbl, i32, i64, P, i32, P]

@@ -283,7 +283,12 @@ class DeepFitFramework:
         (rms and peak of each buffer's time-domain residual and the sample index of the peak
         within the buffer, StandardNLSFitter.fit), after the error columns when both are asked
         for; the DeepFitObject gets attributes of the same names. residual(fit_label) returns
-        the residual record itself."""
+        the residual record itself.
+
+        window='hann' (or 'hamming', 'blackman', 'blackmanharris', or 1-4 cosine-sum coefficients;
+        method 'nls' only): every buffer is demodulated under that window
+        (StandardNLSFitter.fit); the frame and the object keep their columns. Not with
+        errors=True, residuals=True or devices=."""
         _fitters.mark("fit")
         fitter_map = _fitters.FITTER_MAP
         if method not in fitter_map:
@@ -293,6 +298,8 @@ class DeepFitFramework:
             raise ValueError(f"errors=True is available for method 'nls' only, got '{method}'")
         if kwargs.get("residuals") and method != "nls":
             raise ValueError(f"residuals=True is available for method 'nls' only, got '{method}'")
+        if kwargs.get("window") is not None and method != "nls":
+            raise ValueError(f"window= is available for method 'nls' only, got '{method}'")
         hop = kwargs.get("hop")
         if hop is not None and method != "nls":
             raise ValueError(f"hop= is available for method 'nls' only, got '{method}'")
@@ -386,6 +393,8 @@ class DeepFitFramework:
             raise ValueError(f"errors=True is available for method 'nls' only, got '{method}'")
         if kwargs.get("residuals"):
             raise ValueError("residuals=True is not available for fit_many: fit the channels one by one")
+        if kwargs.get("window") is not None:
+            raise ValueError("window= is not available for fit_many: fit the channels one by one")
         raws = [self.raws[l] for l in labels]
         r0 = raws[0]
         if any(r.f_samp != r0.f_samp or r.f_mod != r0.f_mod or r.n_samples() != r0.n_samples() for r in raws):

@@ -48,6 +48,11 @@ hipError_t lcsd_batch_launch(const double* x, int64_t x_stride, const double* y,
                              double* win, double* wsum, int64_t toff0, int64_t tiles_ld, double* tile, int64_t J,
                              double* Sxx, double* Syy, double* Sxy_re, double* Sxy_im, double* coh, double* enbw,
                              hipStream_t st);
+// demod_window.hip: demod_window_kernel<vec, ms, K, sample type xtype>
+hipError_t window_occupancy(int xtype, int vec, int ms, int K, size_t lds, int* per_cu);
+hipError_t window_launch(int xtype, int vec, int ms, int K, int64_t grid, size_t lds, hipStream_t st, const void* x,
+                         int64_t nseg, int64_t seg_stride, int R, int L, int ndata, const double* tab,
+                         const double* wcyc, const double* wbin, double* qi, int64_t qi_ld, double* dc);
 hipError_t snr_gen_launch(const dfmi_snr_params& p, int64_t idx0, int64_t n, double* out, int n_cu, hipStream_t st);
 hipError_t bessel_eval_launch(const double* x, int64_t nx, int nmax, int method, double* out, hipStream_t st);
 hipError_t fisher_launch(const double* params, int64_t n, int64_t ld, int ndata, const double* var, double var_mul,
@@ -202,7 +207,9 @@ struct DeviceState {
   std::map<std::tuple<int, int, uint64_t>, DevBuf> basis;            // (L, ndata, w0 bits); (L, -(8 ndata + no), w0 bits): wide
   std::map<std::tuple<int, uint64_t, uint64_t, uint64_t>, DevBuf> gridtab;  // (ndata, min, max, step)
   std::map<std::tuple<uint64_t, int, int, int>, DevBuf> blocks;     // (w0 bits, ndata, R, B): demod_blocks_kernel's tables
-  std::map<int64_t, DevBuf> pwplan;                                 // n -> numpy pairwise-sum plan
+  std::map<std::tuple<int, int, int, std::array<uint64_t, 4>>, DevBuf> window;  // (R, L, K, coefficient bits): demod_window_kernel's tables
+  std::map<std::tuple<int, int, int, int, size_t>, int> window_occ;  // (xtype, VEC, MAXSLOT, K, LDS bytes) -> blocks per CU
+  std::map<int64_t, DevBuf> pwplan;                                // n -> numpy pairwise-sum plan
   std::map<int, DevBuf> lpsd_rk2;                                    // 0 -> the 1/k^2 table of lpsd_i0
   std::map<std::pair<const void*, int>, int> occupancy;              // (kernel, LDS bytes) -> blocks per CU
   std::mutex mu;               // held by the call that drives this device (CallScope)
@@ -1032,6 +1039,102 @@ int demod_device(const XT* x, int64_t nseg, int64_t stride, int R, int ndata, do
   return DFMI_OK;
 }
 
+// ---- demodulation under a cosine-sum window (demod_window.h demod_window_kernel) ----
+
+// The two tables of demod_window_kernel in one buffer: the per-cycle weights (cycle k < ceil(R / L):
+// cos(2π m k L / R), m = 1..K, then the sines) and, 16-B aligned behind them, the per-bin factors
+// (rows (a_m / a_0) cos(2π m p / R), m = 1..K, then the sine rows, L entries each). The arguments
+// are reduced exactly (m k L mod R, m p mod R), the values formed in long double and every entry
+// rounded once to double.
+int window_tables(int R, int L, int K, const double* a, const double** wcyc, const double** wbin) {
+  const int nc = (R + L - 1) / L;
+  std::array<uint64_t, 4> ab{};
+  for (int m = 0; m <= K; ++m) ab[m] = bits(a[m]);
+  const DevBuf* b;
+  if (int rc = cached_upload(t_ds->window, std::make_tuple(R, L, K, ab), [&](int64_t*) {
+        const long double two_pi = 6.283185307179586476925286766559L;
+        std::vector<double> h((size_t)2 * K * (nc + L));
+        double* hb = h.data() + (size_t)2 * K * nc;
+        for (int m = 1; m <= K; ++m) {
+          for (int k = 0; k < nc; ++k) {
+            const long double ang = two_pi * (long double)(((int64_t)m * k * L) % R) / (long double)R;
+            h[(size_t)k * 2 * K + m - 1] = (double)cosl(ang);
+            h[(size_t)k * 2 * K + K + m - 1] = (double)sinl(ang);
+          }
+          const long double ratio = (long double)a[m] / (long double)a[0];
+          for (int p = 0; p < L; ++p) {
+            const long double ang = two_pi * (long double)(((int64_t)m * p) % R) / (long double)R;
+            hb[(size_t)(m - 1) * L + p] = (double)(ratio * cosl(ang));
+            hb[(size_t)(K + m - 1) * L + p] = (double)(ratio * sinl(ang));
+          }
+        }
+        return h;
+      }, &b))
+    return rc;
+  *wcyc = (const double*)b->p;
+  *wbin = *wcyc + (size_t)2 * K * nc;
+  return DFMI_OK;
+}
+
+// The kernel's 36 instances and their typed launch are compiled in a translation unit of their own
+// (demod_window.hip: dfmi::window_occupancy, dfmi::window_launch), beside this one.
+template <typename XT>
+int launch_window(int VEC, int MS, int K, const XT* x, int64_t nseg, int64_t stride, int R, int L, int ndata,
+                  const double* tab, const double* wcyc, const double* wbin, double* qi, int64_t qi_ld, double* dc,
+                  hipStream_t st, size_t lds) {
+  const int xtype = std::is_same<XT, double>::value ? DFMI_F64 : std::is_same<XT, float>::value ? DFMI_F32 : DFMI_I16;
+  const auto key = std::make_tuple(xtype, VEC, MS, K, lds);
+  auto it = t_ds->window_occ.find(key);
+  if (it == t_ds->window_occ.end()) {  // cached as occupancy() caches it: the query costs host time
+    int v = 0;
+    HIPCHK(dfmi::window_occupancy(xtype, VEC, MS, K, lds, &v));
+    it = t_ds->window_occ.emplace(key, v).first;
+  }
+  const int per_cu = it->second < 1 ? 1 : it->second;
+  const int64_t grid = persistent_grid(t_ds->n_cu, per_cu, (nseg + dfmi::kWavesPerBlock - 1) / dfmi::kWavesPerBlock);
+  HIPCHK(dfmi::window_launch(xtype, VEC, MS, K, grid, lds, st, x, nseg, stride, R, L, ndata, tab, wcyc, wbin, qi, qi_ld,
+                             dc));
+  g_last_demod = "demod_window_kernel<" + std::to_string(VEC) + "," + std::to_string(MS) + "> [" +
+                 (std::is_same<XT, double>::value ? "f64" : std::is_same<XT, float>::value ? "f32" : "i16") +
+                 ", K=" + std::to_string(K) + "]";
+  return DFMI_OK;
+}
+
+// LDS bytes of demod_window_kernel: the basis, and the per-bin factors where they do not stay in registers.
+size_t window_lds(int ms, int K, int L, int ndata) {
+  return ((size_t)2 * ndata * L + (ms >= 4 && K >= 2 ? (size_t)2 * K * L : 0)) * sizeof(double);
+}
+
+// Windowed demodulation of nseg segments (component-major qi, dc), K = number of cosines >= 1, a[0..K]
+// the coefficients. Serves a basis period 2 <= L <= 256·VEC (given or detected) whose tables fit in LDS
+// and R > K; DFMI_ERR_UNSUPPORTED with the reason otherwise.
+template <typename XT>
+int demod_window_device(const XT* x, int64_t nseg, int64_t stride, int R, int ndata, double w0, int period,
+                        const double* a, int K, double* qi, int64_t qi_ld, double* dc, hipStream_t st) {
+  if (nseg == 0) return DFMI_OK;
+  int L = period;
+  if (L == 0) L = detect_period_impl(w0, R, ndata);
+  if (L <= 0)
+    return fail(DFMI_ERR_UNSUPPORTED, "windowed demodulation needs a basis period of a whole number of samples: none "
+                                      "found for this w0 (the block kernel has no windowed form)");
+  const bool vec2 = vec2_ok(x, stride, L);
+  const int VEC = vec2 ? 2 : 1;
+  if (L < 2 || L > 256 * VEC)
+    return fail(DFMI_ERR_UNSUPPORTED, "windowed demodulation: basis period L = " + std::to_string(L) +
+                                          " outside 2.." + std::to_string(256 * VEC) +
+                                          (vec2 ? "" : " (512 needs pair-aligned segments and an even L)"));
+  if (R <= K) return fail(DFMI_ERR_UNSUPPORTED, "windowed demodulation: R must exceed the number of window cosines");
+  const int ms = (L + 64 * VEC - 1) / (64 * VEC) <= 2 ? 2 : 4;
+  const size_t lds = window_lds(ms, K, L, ndata);
+  if (lds > t_ds->lds_per_block)
+    return fail(DFMI_ERR_UNSUPPORTED, "windowed demodulation: too many harmonics for LDS (" + std::to_string(lds) +
+                                          " bytes of basis and window tables)");
+  const double *tab = nullptr, *wcyc = nullptr, *wbin = nullptr;
+  if (int rc = basis_table(L, ndata, w0, &tab)) return rc;
+  if (int rc = window_tables(R, L, K, a, &wcyc, &wbin)) return rc;
+  return launch_window(VEC, ms, K, x, nseg, stride, R, L, ndata, tab, wcyc, wbin, qi, qi_ld, dc, st, lds);
+}
+
 // ---- frame-interleaved records: x[(b·R + t)·frame_stride + c] (include/dfmi.h) ----
 constexpr int kFramesMaxCh = 32;  // deinterleave_frames_kernel's tile: 256 frames x nch samples in LDS (64 KB of doubles)
 
@@ -1598,6 +1701,50 @@ int nls_record_device(const XT* x, int64_t nrec, int64_t rec_stride, int64_t nbu
   // the rest, seeded with each record's buffer-0 result (read on device: no host sync)
   return lm_device(qi, rows ? qs : nseg, ndata, nrec, nbuf, 1, nbuf - 1, nchunk, out, nbuf, out_ld, nullptr, c,
                    jtab, out, out_ld, fitok, st, rows);
+}
+
+// The record call under a window: the windowed demodulation of every segment (segment s of record r at
+// x + r·rec_stride + s·hop) into component-major QI and dc, then the fit from those QI: sequential, one
+// warm-start chain per record from its guess; parallel, segment 0 of every record from its guess, whose
+// result seeds the record's other segments in nchunk chains (the two-kernel sequence of
+// nls_record_device, with the seed fitted from the windowed QI).
+template <typename XT>
+int nls_record_window_device(const XT* x, int64_t nrec, int64_t rec_stride, int64_t nbuf, int R, int hop, int ndata,
+                             double w0, int period, const double* a, int K, const double* init_guess_host,
+                             int parallel, int64_t nchunk, const dfmi_lm_config& cfg, const dfmi::LMConst& c,
+                             double* out, int32_t* fitok, hipStream_t st) {
+  const int64_t nseg = nrec * nbuf;
+  if (nseg == 0) return DFMI_OK;
+  const double* jtab = nullptr;
+  int rc = grid_table(ndata, cfg, &jtab);
+  if (rc) return rc;
+  const double* gdev = nullptr;
+  if (nrec > 8) {
+    void* gw = nullptr;
+    if ((rc = workspace("guess", (size_t)nrec * 4 * sizeof(double), &gw))) return rc;
+    HIPCHK(hipMemcpyAsync(gw, init_guess_host, (size_t)nrec * 4 * sizeof(double), hipMemcpyHostToDevice, st));
+    gdev = (const double*)gw;
+  }
+  void* w = nullptr;
+  if ((rc = workspace("qi", (size_t)2 * ndata * nseg * sizeof(double), &w))) return rc;
+  double* qi = (double*)w;
+  double* dc = out + 4 * nseg;
+  if (nrec == 1 || rec_stride == nbuf * (int64_t)hop) {
+    rc = demod_window_device(x, nseg, hop, R, ndata, w0, period, a, K, qi, nseg, dc, st);
+  } else {
+    for (int64_t r = 0; r < nrec && rc == 0; ++r)
+      rc = demod_window_device(x + r * rec_stride, nbuf, hop, R, ndata, w0, period, a, K, qi + r * nbuf, nseg,
+                               dc + r * nbuf, st);
+  }
+  if (rc) return rc;
+  if (!parallel)
+    return lm_device(qi, nseg, ndata, nrec, nbuf, 0, nbuf, 1, gdev, 4, 1, init_guess_host, c, jtab, out, nseg, fitok,
+                     st);
+  if ((rc = lm_device(qi, nseg, ndata, nrec, nbuf, 0, 1, 1, gdev, 4, 1, init_guess_host, c, jtab, out, nseg, fitok, st)))
+    return rc;
+  if (nbuf <= 1) return DFMI_OK;
+  return lm_device(qi, nseg, ndata, nrec, nbuf, 1, nbuf - 1, nchunk, out, nbuf, nseg, nullptr, c, jtab, out, nseg,
+                   fitok, st);
 }
 
 }  // namespace
@@ -2315,6 +2462,72 @@ int nls_record_hop_impl(const XT* x, int64_t nrec, int64_t rec_stride, int64_t n
     return rc;
   return sg.finish();
 }
+
+// Bodies of dfmi_demod_window / dfmi_nls_record_window over the sample type XT (two or more
+// coefficients; one coefficient is forwarded to the rectangular calls by the entry points).
+int bad_window(const double* wcoef, int32_t nwcoef) {
+  if (nwcoef < 1 || nwcoef > 4) return fail(DFMI_ERR_ARG, "window: 1 <= nwcoef <= 4");
+  if (!wcoef) return fail(DFMI_ERR_ARG, "window: null wcoef");
+  for (int i = 0; i < nwcoef; ++i)
+    if (!std::isfinite(wcoef[i])) return fail(DFMI_ERR_ARG, "window: non-finite coefficient");
+  if (wcoef[0] == 0.0) return fail(DFMI_ERR_ARG, "window: wcoef[0] must not be zero");
+  return DFMI_OK;
+}
+
+template <typename XT>
+int demod_window_impl(const XT* x, int64_t nseg, int64_t seg_stride, int32_t R, int32_t ndata, double w0,
+                      int32_t period, const double* wcoef, int32_t nwcoef, double* qi, double* dc, int32_t mem,
+                      void* stream) {
+  CallScope cs(stream);
+  if (nseg > 0 && (!x || !qi || !dc)) return fail(DFMI_ERR_ARG, "null pointer");
+  int rc = ensure_init();
+  if (rc) return rc;
+  if (nseg == 0) return DFMI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  Staging sg(mem, st);
+  const XT* dx;
+  double *dq, *dd;
+  if ((rc = sg.in("d_x", x, (size_t)((nseg - 1) * seg_stride + R) * sizeof(XT), &dx))) return rc;
+  if ((rc = sg.out("d_qi", qi, (size_t)2 * ndata * nseg * 8, &dq))) return rc;
+  if ((rc = sg.out("d_dc", dc, (size_t)nseg * 8, &dd))) return rc;
+  if ((rc = demod_window_device(dx, nseg, seg_stride, R, ndata, w0, period, wcoef, nwcoef - 1, dq, nseg, dd, st)))
+    return rc;
+  return sg.finish();
+}
+
+template <typename XT>
+int nls_record_window_impl(const XT* x, int64_t nrec, int64_t rec_stride, int64_t nseg, int32_t R, int32_t hop,
+                           int32_t ndata, double w0, int32_t period, const double* wcoef, int32_t nwcoef,
+                           const double* init_guess, int32_t parallel, int64_t nchunk, const dfmi_lm_config* cfg,
+                           double* out, int32_t* fitok, int32_t mem, void* stream) {
+  CallScope cs(stream);
+  const int64_t ntot = nrec * nseg;
+  if (ntot > 0 && (!x || !init_guess || !out || !fitok)) return fail(DFMI_ERR_ARG, "null pointer");
+  dfmi_lm_config dcfg;
+  if (!cfg) {
+    dfmi_lm_config_default(&dcfg);
+    cfg = &dcfg;
+  }
+  dfmi::LMConst c;
+  int rc = to_lmconst(cfg, &c);
+  if (rc) return rc;
+  if ((rc = ensure_init())) return rc;
+  if (ntot == 0) return DFMI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  Staging sg(mem, st);
+  const int64_t ext = (nseg - 1) * (int64_t)hop + R;
+  const int64_t rs = nrec > 1 ? rec_stride : ext;
+  const XT* dx;
+  double* dout;
+  int32_t* dst;
+  if ((rc = sg.in("n_x", x, (size_t)((nrec - 1) * rs + ext) * sizeof(XT), &dx))) return rc;
+  if ((rc = sg.out("n_out", out, (size_t)6 * ntot * 8, &dout))) return rc;
+  if ((rc = sg.out("n_status", fitok, (size_t)ntot * 4, &dst))) return rc;
+  if ((rc = nls_record_window_device(dx, nrec, rs, nseg, R, hop, ndata, w0, period, wcoef, nwcoef - 1, init_guess,
+                                     parallel, nchunk, *cfg, c, dout, dst, st)))
+    return rc;
+  return sg.finish();
+}
 }  // namespace
 
 extern "C" {
@@ -2562,6 +2775,42 @@ int dfmi_nls_record_hop(const void* x, int32_t xtype, int64_t nrec, int64_t rec_
                                parallel, nchunk, cfg, out, fitok, mem, stream);
   return nls_record_hop_impl((const float*)x, nrec, rec_stride, nseg, R, hop, ndata, w0, period, init_guess, parallel,
                              nchunk, cfg, out, fitok, mem, stream);
+}
+
+int dfmi_demod_window(const void* x, int32_t xtype, int64_t nseg, int64_t seg_stride, int32_t R, int32_t ndata,
+                      double w0, int32_t period, const double* wcoef, int32_t nwcoef, double* qi, double* dc,
+                      int32_t mem, void* stream) {
+  if (bad_xtype(xtype)) return fail(DFMI_ERR_ARG, "unknown sample type");
+  if (int rc = bad_window(wcoef, nwcoef)) return rc;
+  if (nseg < 0 || R <= 0 || ndata <= 0 || seg_stride < 1) return fail(DFMI_ERR_ARG, "bad demod geometry");
+  if (nwcoef == 1 && seg_stride >= R)  // a constant window: the rectangular call itself
+    return dfmi_demod_typed(x, xtype, nseg, seg_stride, R, ndata, w0, period, qi, dc, mem, stream);
+  if (nwcoef == 1) return dfmi_demod_hop(x, xtype, 1, 0, nseg, R, (int32_t)seg_stride, ndata, w0, period, qi, dc, mem, stream);
+  if (xtype == DFMI_F64)
+    return demod_window_impl((const double*)x, nseg, seg_stride, R, ndata, w0, period, wcoef, nwcoef, qi, dc, mem, stream);
+  if (xtype == DFMI_I16)
+    return demod_window_impl((const int16_t*)x, nseg, seg_stride, R, ndata, w0, period, wcoef, nwcoef, qi, dc, mem, stream);
+  return demod_window_impl((const float*)x, nseg, seg_stride, R, ndata, w0, period, wcoef, nwcoef, qi, dc, mem, stream);
+}
+
+int dfmi_nls_record_window(const void* x, int32_t xtype, int64_t nrec, int64_t rec_stride, int64_t nseg, int32_t R,
+                           int32_t hop, int32_t ndata, double w0, int32_t period, const double* wcoef, int32_t nwcoef,
+                           const double* init_guess, int32_t parallel, int64_t nchunk, const dfmi_lm_config* cfg,
+                           double* out, int32_t* fitok, int32_t mem, void* stream) {
+  if (bad_xtype(xtype)) return fail(DFMI_ERR_ARG, "unknown sample type");
+  if (int rc = bad_window(wcoef, nwcoef)) return rc;
+  if (int rc = bad_hop(nrec, rec_stride, nseg, R, hop, ndata)) return rc;
+  if (nwcoef == 1)  // a constant window: the rectangular call itself
+    return dfmi_nls_record_hop(x, xtype, nrec, rec_stride, nseg, R, hop, ndata, w0, period, init_guess, parallel, nchunk,
+                               cfg, out, fitok, mem, stream);
+  if (xtype == DFMI_F64)
+    return nls_record_window_impl((const double*)x, nrec, rec_stride, nseg, R, hop, ndata, w0, period, wcoef, nwcoef,
+                                  init_guess, parallel, nchunk, cfg, out, fitok, mem, stream);
+  if (xtype == DFMI_I16)
+    return nls_record_window_impl((const int16_t*)x, nrec, rec_stride, nseg, R, hop, ndata, w0, period, wcoef, nwcoef,
+                                  init_guess, parallel, nchunk, cfg, out, fitok, mem, stream);
+  return nls_record_window_impl((const float*)x, nrec, rec_stride, nseg, R, hop, ndata, w0, period, wcoef, nwcoef,
+                                init_guess, parallel, nchunk, cfg, out, fitok, mem, stream);
 }
 
 int32_t dfmi_qi_row_stride(int32_t ndata) { return ndata > 0 ? dfmi_row_stride((int)ndata) : 0; }

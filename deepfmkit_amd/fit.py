@@ -66,13 +66,33 @@ def _lm_config_build() -> _lib.LMConfig:
     return cfg
 
 
-def demodulate(buffers, ndata: int, w0: float, period: int = 0):
+def demodulate(buffers, ndata: int, w0: float, period: int = 0, window=None):
     """QI of every row of `buffers` (nseg, R) float64 -> (QI (nseg, 2*ndata), dc (nseg,)).
 
     QI row layout is the reference's [Q_1..Q_ndata, I_1..I_ndata] (fitters.py:45-49).
     A float32 array is sent as it is (dfmi_demod_typed: the kernels widen on load, the same
-    bits as for the widened array); every other dtype is widened to float64 here."""
+    bits as for the widened array); every other dtype is widened to float64 here.
+
+    window (None: the rectangular window, the call as it always was): 'hann', 'hamming',
+    'blackman', 'blackmanharris' or 1-4 coefficients a_m of w[t] = sum_m a_m cos(2 pi m t / R);
+    Q, I and dc are then the w-weighted means (dfmi_demod_window; float32 and int16 arrays are
+    sent as they are). The fit's model stays unbiased only when a row holds a whole number n of
+    modulation periods with n > K, the number of cosines of the window."""
     lib = _lib.load()
+    if window is not None:
+        a = _lib.window_coefficients(window)
+        typed = isinstance(buffers, np.ndarray) and buffers.dtype in (np.float32, np.int16)
+        x = np.ascontiguousarray(buffers, dtype=buffers.dtype if typed else np.float64)
+        if x.ndim != 2:
+            raise ValueError("buffers must be (nseg, R)")
+        nseg, R = x.shape
+        xtype = {"float64": _lib.DFMI_F64, "float32": _lib.DFMI_F32, "int16": _lib.DFMI_I16}[str(x.dtype)]
+        qi_cm = np.empty((2 * ndata, nseg))
+        dc = np.empty(nseg)
+        _lib.check(lib.dfmi_demod_window(_lib.ptr(x), xtype, nseg, R, R, ndata, float(w0), int(period), _lib.ptr(a),
+                                         a.size, _lib.ptr(qi_cm), _lib.ptr(dc), _lib.DFMI_MEM_HOST, None),
+                   "dfmi_demod_window")
+        return np.ascontiguousarray(qi_cm.T), dc
     f32 = isinstance(buffers, np.ndarray) and buffers.dtype == np.float32
     x = np.ascontiguousarray(buffers, dtype=np.float32 if f32 else np.float64)
     if x.ndim != 2:

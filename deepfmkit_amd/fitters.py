@@ -203,7 +203,7 @@ def residual_record(x, f_samp, f_mod, R, params, dc, hop=None):
 
 
 def nls_records(records, f_samp, f_mod, R, nbuf, ndata=10, init_guess=(1.6, 6.0, 0.0, 0.0), parallel=True,
-                n_cores=None, errors=False, hop=None, residuals=False):
+                n_cores=None, errors=False, hop=None, residuals=False, window=None):
     """Run the StandardNLSFitter pipeline on one or more equal-length records in ONE
     GPU call (config 3: several channels as one batch).
 
@@ -225,7 +225,17 @@ def nls_records(records, f_samp, f_mod, R, nbuf, ndata=10, init_guess=(1.6, 6.0,
     errors=True: a third value, the (4, nrec*nbuf) standard errors of amp, m, phi, psi
     (_segment_errors; NaN where J^T J at the fitted point has no inverse); ndata >= 3.
     residuals=True: one more value (the last), the (3, nrec*nbuf) block [rms, peak, ipeak] of each
-    segment's time-domain residual (_segment_residuals: one more pass over the samples)."""
+    segment's time-domain residual (_segment_residuals: one more pass over the samples).
+    window (None: the rectangular window, the call as it always was): 'hann', 'hamming',
+    'blackman', 'blackmanharris' or 1-4 coefficients a_m of w[t] = sum_m a_m cos(2 pi m t / R):
+    every segment is demodulated under that window (dfmi_nls_record_window), which keeps what is
+    not a modulation harmonic (drift, mains pickup, a second tone) out of the fitted QI; with hop=
+    too. The model stays unbiased only when a segment holds a whole number n of modulation periods
+    with n > K, the number of cosines of the window (Hann 1, Blackman-Harris 3). Not with
+    errors=True or residuals=True (ValueError): both weigh the samples equally."""
+    win = None if window is None else _lib.window_coefficients(window)
+    if win is not None and (errors or residuals):
+        raise ValueError("window= is not available with errors=True or residuals=True")
     if errors:
         _check_errors_ndata(ndata)
     lib = _lib.load()
@@ -270,7 +280,12 @@ def nls_records(records, f_samp, f_mod, R, nbuf, ndata=10, init_guess=(1.6, 6.0,
         ok = torch.empty(nseg, dtype=torch.int32, device=x.device)
         mark("alloc")
         with _on_device(x):
-            if hop is not None:
+            if win is not None:
+                rc = lib.dfmi_nls_record_window(x.data_ptr(), xtype, nrec, rec_stride, nbuf, R, R if hop is None else hop,
+                                                ndata, w0, 0, _lib.ptr(win), win.size, _lib.ptr(g),
+                                                1 if parallel else 0, max(nchunk, 1), cfg, out.data_ptr(),
+                                                ok.data_ptr(), _lib.DFMI_MEM_DEVICE, _torch_stream(x.device))
+            elif hop is not None:
                 rc = lib.dfmi_nls_record_hop(x.data_ptr(), xtype, nrec, rec_stride, nbuf, R, hop, ndata, w0, 0,
                                              _lib.ptr(g), 1 if parallel else 0, max(nchunk, 1), cfg, out.data_ptr(),
                                              ok.data_ptr(), _lib.DFMI_MEM_DEVICE, _torch_stream(x.device))
@@ -296,7 +311,12 @@ def nls_records(records, f_samp, f_mod, R, nbuf, ndata=10, init_guess=(1.6, 6.0,
         return (out, ok) + more
     out = np.empty((6, nseg))
     ok = np.empty(nseg, dtype=np.int32)
-    if hop is not None:
+    if win is not None:
+        rc = lib.dfmi_nls_record_window(_lib.ptr(x), _xtype(x.dtype), nrec, rec_stride, nbuf, R,
+                                        R if hop is None else hop, ndata, w0, 0, _lib.ptr(win), win.size, _lib.ptr(g),
+                                        1 if parallel else 0, max(nchunk, 1), cfg, _lib.ptr(out), _lib.ptr(ok),
+                                        _lib.DFMI_MEM_HOST, None)
+    elif hop is not None:
         rc = lib.dfmi_nls_record_hop(_lib.ptr(x), _xtype(x.dtype), nrec, rec_stride, nbuf, R, hop, ndata, w0, 0,
                                      _lib.ptr(g), 1 if parallel else 0, max(nchunk, 1), cfg, _lib.ptr(out),
                                      _lib.ptr(ok), _lib.DFMI_MEM_HOST, None)
@@ -324,15 +344,17 @@ def _no_residuals(residuals, what):
 
 
 def nls_frames(frames, f_samp, f_mod, R, nbuf, ndata=10, init_guess=(1.6, 6.0, 0.0, 0.0), parallel=True,
-               n_cores=None, errors=False, residuals=False):
+               n_cores=None, errors=False, residuals=False, window=None):
     """nls_records on the nch records that frame-interleaved samples hold, with no transposed
     copy: frames is a 2-D (N >= nbuf*R, nch) numpy array or CUDA tensor with stride(1) == 1
     (row t = sample t of every channel, as a digitiser delivers them; stride(0) > nch: padded
     frames) of float64, float32 or int16. Returns what nls_records returns for the planar records
     frames[:, c], channel by channel (segment c*nbuf + b), bit for bit. int16 frames of 2, 4 or
     8 channels are folded as they lie (dfmi_nls_record_frames, include/dfmi.h); anything else
-    is de-interleaved on the device first. residuals=True is refused (ValueError)."""
+    is de-interleaved on the device first. residuals=True and window= are refused (ValueError)."""
     _no_residuals(residuals, "frame-interleaved records (nls_frames)")
+    if window is not None:
+        raise ValueError("window= is not available for frame-interleaved records (nls_frames)")
     if errors:
         _check_errors_ndata(ndata)
     dev = _is_device_tensor(frames)
@@ -595,10 +617,18 @@ class StandardNLSFitter(BaseFitter):
     residuals=True appends the float64 columns res_rms, res_peak, res_peak_t (after the error
     columns when both are asked for): rms and peak of each buffer's time-domain residual and the
     sample index of the peak within the buffer (dfmi_residual on the record's side, behind the
-    fit); not with devices= and not for a column of a frames block."""
+    fit); not with devices= and not for a column of a frames block.
+    window='hann' (or 'hamming', 'blackman', 'blackmanharris', or 1-4 cosine-sum coefficients):
+    every buffer is demodulated under that window (nls_records' window, with hop= too); not with
+    errors=True, residuals=True or devices=."""
 
     def fit(self, main_raw, **kwargs) -> pd.DataFrame:
         n = self.config["n"]
+        window = kwargs.get("window")
+        if window is not None:
+            _lib.window_coefficients(window)
+            if kwargs.get("errors") or kwargs.get("residuals") or kwargs.get("devices") is not None:
+                raise ValueError("window= is not available with errors=True, residuals=True or devices=")
         ndata = int(kwargs.pop("ndata", self.config.get("ndata", 10)))
         parallel = kwargs.get("parallel", True)
         init_a = kwargs.get("init_a", 1.6)
@@ -625,7 +655,7 @@ class StandardNLSFitter(BaseFitter):
             res = nls_records(xs.reshape(1, N), main_raw.f_samp, main_raw.f_mod, R, None, ndata,
                               (init_a, init_m, 0.0, init_psi), parallel=parallel,
                               n_cores=kwargs.get("n_cores") if parallel else None, errors=errors, hop=int(hop),
-                              residuals=residuals)
+                              residuals=residuals, window=window)
             if errors or residuals:
                 return frame_with_errors(res[0], res[1], res[2] if errors else None, res[-1] if residuals else None)
             return frame_from(*res, tau_divisor(main_raw))
@@ -643,6 +673,12 @@ class StandardNLSFitter(BaseFitter):
         mark("fitter_args")
         fit_records = nls_records
         if devices is None:
+            if window is not None:  # (a column of a frames block is copied: nls_frames has no window)
+                one = (x.contiguous() if _is_device_tensor(x) else x).reshape(1, N)
+                cols, ok = nls_records(one, main_raw.f_samp, main_raw.f_mod, R, nbuf, ndata,
+                                       (init_a, init_m, 0.0, init_psi), parallel=parallel,
+                                       n_cores=kwargs.get("n_cores") if parallel else None, window=window)
+                return frame_from(cols, ok, tau_divisor(main_raw))
             if _is_device_tensor(x) and N > 1 and x.stride(0) != 1:
                 # a column of a frames block (load_frames): a one-channel frames call, no copy here
                 one, fit_records = x[:, None], nls_frames

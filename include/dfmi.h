@@ -249,6 +249,35 @@ int dfmi_nls_record_hop(const void* x, int32_t xtype, int64_t nrec, int64_t rec_
                         int32_t parallel, int64_t nchunk, const dfmi_lm_config* cfg, double* out, int32_t* fitok,
                         int32_t mem, void* stream);
 
+/* Demodulation under a cosine-sum window (Hann, Hamming, Blackman, Blackman-Harris, ...):
+ *   w[t] = sum_{m=0..K} wcoef[m] cos(2 pi m t / R), t = 0..R-1 (the periodic, DFT-even form), K = nwcoef - 1 <= 3,
+ *   Q_h = sum_t w[t] x[t] cos(fl(h w0) t) / sum_t w[t], I_h with sin, dc = sum w x / sum w   (sum w = R wcoef[0]).
+ * Layouts, mem, the staging of host records in their own type and the meaning of parallel / nchunk are
+ * those of dfmi_demod_typed and dfmi_nls_record_hop; in the demodulation call any seg_stride >= 1 is
+ * legal (overlapped, contiguous or gapped segments), in the record call segment s of record r starts
+ * at r * rec_stride + s * hop, 1 <= hop <= R (hop == R: disjoint buffers). The record call demodulates
+ * every segment under the window, fits segment 0 of every record from its guess and the others from
+ * that result (parallel) or as one warm-start chain (sequential), all from the windowed QI.
+ * For a signal that repeats with the modulation over a whole number n = R / L of basis periods with
+ * n > K, the windowed QI are those of the rectangular window (the fit's model is unbiased); with
+ * n <= K or a ragged R the model is biased and the condition is the caller's.
+ * nwcoef == 1 forwards to dfmi_demod_typed / dfmi_nls_record_hop (a constant window: the same bits).
+ * DFMI_ERR_ARG, before any device work: nwcoef outside 1..4, a null wcoef, wcoef[0] == 0, a
+ * non-finite coefficient, an unknown xtype, bad geometry (dfmi_nls_record_hop's rules).
+ * demod_window_kernel (reported as "demod_window_kernel<VEC,MAXSLOT> [f64|f32|i16, K=...]") folds every
+ * sample into 1 + 2K sets of phase bins with wave-uniform weights and rotates them into the windowed
+ * bins once per segment. It needs a basis period L of a whole number of samples (given or detected),
+ * 2 <= L <= 512 for pair-aligned segments at an even L and <= 256 otherwise, its tables within the
+ * workgroup's LDS, and R > K; everything else is DFMI_ERR_UNSUPPORTED with the reason in
+ * dfmi_last_error (no period, a larger L, too many harmonics for LDS). */
+int dfmi_demod_window(const void* x, int32_t xtype, int64_t nseg, int64_t seg_stride, int32_t R, int32_t ndata,
+                      double w0, int32_t period, const double* wcoef, int32_t nwcoef, double* qi, double* dc,
+                      int32_t mem, void* stream);
+int dfmi_nls_record_window(const void* x, int32_t xtype, int64_t nrec, int64_t rec_stride, int64_t nseg, int32_t R,
+                           int32_t hop, int32_t ndata, double w0, int32_t period, const double* wcoef,
+                           int32_t nwcoef, const double* init_guess, int32_t parallel, int64_t nchunk,
+                           const dfmi_lm_config* cfg, double* out, int32_t* fitok, int32_t mem, void* stream);
+
 /* Per-sample EKF (fitters.py:214-320) over nrec independent channels, each a serial
  * chain over its samples: up to 16 x CUs channels one 16-lane DPP row per channel (4 per
  * wave; ekf_rot_kernel with sin / cos by rotation between anchors when R % 4 == 0, else
