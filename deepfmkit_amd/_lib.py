@@ -35,7 +35,7 @@ SYMBOLS = ("dfmi_lm_config_default", "dfmi_demod", "dfmi_lm", "dfmi_nls_record",
            "dfmi_fisher", "dfmi_lpsd_plan", "dfmi_lpsd", "dfmi_plnoise_design", "dfmi_plnoise",
            "dfmi_synth_asd_coloured", "dfmi_lcsd", "dfmi_demod_frames", "dfmi_nls_record_frames",
            "dfmi_demod_hop", "dfmi_nls_record_hop", "dfmi_residual", "dfmi_demod_window",
-           "dfmi_nls_record_window")
+           "dfmi_nls_record_window", "dfmi_unwrap")
 
 # cosine-sum windows by name: w[t] = sum_m a_m cos(2 pi m t / R) (dfmi_demod_window)
 WINDOWS = {"hann": (0.5, -0.5), "hamming": (0.54, -0.46), "blackman": (0.42, -0.5, 0.08),
@@ -273,6 +273,8 @@ def load():
         lib.dfmi_fisher.restype = ctypes.c_int
         lib.dfmi_residual.argtypes = [P, i32, i64, i64, i32, dbl, i32, P, i64, P, P, P, P, P, i64, i32, P]
         lib.dfmi_residual.restype = ctypes.c_int
+        lib.dfmi_unwrap.argtypes = [P, i64, i64, i64, dbl, P, i64, i32, i32, P, i64, P, i64, i32, P]
+        lib.dfmi_unwrap.restype = ctypes.c_int
         lib.dfmi_lpsd_plan.argtypes = [i64, dbl, dbl, dbl, i64, i64, i64, P, P, P, P, P, i64]
         lib.dfmi_lpsd_plan.restype = i64
         lib.dfmi_lpsd.argtypes = [P, i64, i64, i64, dbl, P, P, P, i64, i32, dbl, P, P, i32, P]

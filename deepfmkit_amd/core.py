@@ -450,6 +450,35 @@ class DeepFitFramework:
         params = np.stack([fit.amp, fit.m, fit.phi, fit.psi])
         return _fitters.residual_record(x, raw.f_samp, raw.f_mod, fit.R, params, fit.dc, hop=fit.hop)
 
+    def unwrap(self, labels=None, which="phi", max_status=1, fill="nan"):
+        """Unwraps the fitted `which` of the fits under `labels`, or of all fits, by 2 pi
+        (deepfmkit_amd.series.unwrap): sets each fit's `<which>_unwrapped` and
+        returns {label: array}. Buffers whose fitok exceeds max_status (2: still bad after the
+        retry) are stepped over, and are NaN (fill="nan") or hold the last good value
+        (fill="hold") in the result; a fit without a fitok column has no such buffers. Fits of
+        equal length go through one GPU call. calc_lpsd(which="phi_unwrapped") then reads the
+        result. A label without a fit logs calc_lpsd's warning and is left out."""
+        from .series import unwrap
+        groups = {}
+        for label in (self.fits if labels is None else labels):
+            try:
+                fit = self.fits[label]
+                x = np.asarray(getattr(fit, which), dtype=np.float64).reshape(-1)
+            except (KeyError, TypeError, AttributeError):
+                log.warning("Specified label is invalid!")
+                continue
+            df = self.fits_df.get(label)
+            ok = df["fitok"].to_numpy() if df is not None and "fitok" in df.columns else np.zeros(x.size)
+            groups.setdefault(x.size, {})[label] = (fit, x, np.asarray(ok, dtype=np.int32).reshape(-1))
+        out = {}
+        for members in groups.values():
+            y = unwrap(np.stack([x for _, x, _ in members.values()]), status=np.stack([s for _, _, s in members.values()]),
+                       max_status=max_status, fill=fill)
+            for i, (label, (fit, _, _)) in enumerate(members.items()):
+                out[label] = np.ascontiguousarray(y[i])
+                setattr(fit, which + "_unwrapped", out[label])
+        return out
+
     # --- spectra (core.py:590-609) ------------------------------------------------
     def calc_lpsd(self, labels=None, which="phi"):
         """LPSD of the fitted `which` ('phi' in the reference) of the fits under `labels`, or of

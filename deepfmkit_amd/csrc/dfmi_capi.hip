@@ -35,6 +35,7 @@
 #include "wdfmi.h"
 #include "lpsd.h"
 #include "residual.h"
+#include "unwrap.h"
 
 namespace dfmi {
 hipError_t lpsd_batch_launch(const double* x, int64_t nser, int64_t ser_stride, int64_t N, double fs,
@@ -147,6 +148,7 @@ struct Tuning {
   int ekf_pit_fused = 1;      // 1: EKF + fold in one kernel per pass (ekf_pit_pass_kernel); 0: separate kernels
   int lpsd_batch_mb = 512;    // dfmi_lpsd: MiB of window + tile workspace per batch of frequencies (a batch holds
                               // at least one frequency; 0 = one frequency per batch); same bits
+  int unwrap_path = 0;        // dfmi_unwrap: 1 the series kernel, 2 the tiled path, 0 by unwrap_pick; same bits
 };
 Tuning g_tune;
 
@@ -1800,7 +1802,8 @@ const std::map<std::string, Knob>& knobs() {
       {"ekf_pit_measure", {&Tuning::ekf_pit_measure, {0, 1}}},
       {"ekf_pit_head", {&Tuning::ekf_pit_head, {}}},
       {"ekf_pit_fused", {&Tuning::ekf_pit_fused, {0, 1}}},
-      {"lpsd_batch_mb", {&Tuning::lpsd_batch_mb, {}}}};
+      {"lpsd_batch_mb", {&Tuning::lpsd_batch_mb, {}}},
+      {"unwrap_path", {&Tuning::unwrap_path, {0, 1, 2}}}};
   return k;
 }
 // np.mean / np.var of nrec device records on st (moments.hip), numpy-exact.
@@ -3182,6 +3185,71 @@ int dfmi_residual(const void* x, int32_t xtype, int64_t nseg, int64_t seg_stride
                                t_ds->n_cu, st));
   if (resid && sg.host)
     HIPCHK(hipMemcpy2DAsync(resid, (size_t)resid_stride * 8, dres, (size_t)dres_stride * 8, (size_t)R * 8, (size_t)nseg,
+                            hipMemcpyDeviceToHost, st));
+  return sg.finish();
+}
+
+// dfmi_unwrap's geometry: the series kernel (1) keeps a whole series in one workgroup, which walks
+// a tile in ~3 us whatever else runs, so it needs several workgroups per CU to fill the device;
+// below that, and with more than one tile, the tiled path (2) spreads every series over the
+// device. Measured at N = 100k: within 5 % at 512 series (2 per CU: 0.41 against 0.39-0.40
+// ms), the series kernel 21-24 % ahead at 1,024, the tiled path 1.5x ahead at 256. A single tile is
+// the series kernel's, and so is a call whose tile count does not fit one grid.
+static int unwrap_pick(int forced, int64_t nser, int64_t ntile, int n_cu) {
+  if (nser * ntile > INT32_MAX) return 1;
+  if (forced == 1 || forced == 2) return forced;
+  return ntile == 1 || nser >= 2 * (int64_t)n_cu ? 1 : 2;
+}
+
+int dfmi_unwrap(const double* x, int64_t nser, int64_t ser_stride, int64_t N, double period, const int32_t* status,
+                int64_t status_stride, int32_t max_status, int32_t fill, double* y, int64_t y_stride, int64_t* cycles,
+                int64_t cycles_stride, int32_t mem, void* stream) {
+  CallScope cs(stream);
+  if (!(period > 0.0) || !std::isfinite(period)) return fail(DFMI_ERR_ARG, "unwrap: period must be positive and finite");
+  if (nser < 0 || N < 0 || N > INT32_MAX) return fail(DFMI_ERR_ARG, "bad unwrap geometry (nser >= 0, 0 <= N < 2^31)");
+  if (nser > 1 && (ser_stride < N || (status && status_stride < N) || (y && y_stride < N) || (cycles && cycles_stride < N)))
+    return fail(DFMI_ERR_ARG, "unwrap: a row stride is smaller than N");
+  if (fill < 0 || fill > 1) return fail(DFMI_ERR_ARG, "unwrap: fill must be 0 (NaN) or 1 (hold)");
+  if (!y && !cycles) return fail(DFMI_ERR_ARG, "unwrap: one of y, cycles is required");
+  if (y && y == x) return fail(DFMI_ERR_ARG, "unwrap: y == x (in place is not supported)");
+  if (nser * N > 0 && !x) return fail(DFMI_ERR_ARG, "null pointer");
+  if (nser > INT32_MAX) return fail(DFMI_ERR_UNSUPPORTED, "unwrap: more than 2^31 - 1 series");
+  int rc = ensure_init();
+  if (rc) return rc;
+  if (nser == 0 || N == 0) return DFMI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  Staging sg(mem, st);
+  const int64_t xs = nser > 1 ? ser_stride : N, ss = nser > 1 ? status_stride : N;
+  int64_t ys = nser > 1 ? y_stride : N, cys = nser > 1 ? cycles_stride : N;
+  const double* dx;
+  const int32_t* dstat = nullptr;
+  double* dy = y;
+  int64_t* dc = cycles;
+  if ((rc = sg.in("uw_x", x, (size_t)((nser - 1) * xs + N) * 8, &dx))) return rc;
+  if (status && (rc = sg.in("uw_status", status, (size_t)((nser - 1) * ss + N) * 4, &dstat))) return rc;
+  // host results are staged by hand: rows packed at an even stride on the device, copied back row
+  // by row (a strided 2-D copy), so the caller's memory between its rows is left alone
+  const int64_t packed = N + (N & 1);
+  if (sg.host && y) {
+    if ((rc = workspace("uw_y", (size_t)nser * packed * 8, (void**)&dy))) return rc;
+  }
+  if (sg.host && cycles) {
+    if ((rc = workspace("uw_cycles", (size_t)nser * packed * 8, (void**)&dc))) return rc;
+  }
+  const int64_t dys = sg.host ? packed : ys, dcs = sg.host ? packed : cys;
+  const int64_t ntile = dfmi::unwrap_ntile(N);
+  const int path = unwrap_pick(t_tune.unwrap_path, nser, ntile, t_ds->n_cu);
+  dfmi::UwState* tiles = nullptr;
+  double* lead = nullptr;
+  if (path == 2) {
+    if ((rc = workspace("uw_tiles", (size_t)nser * ntile * sizeof(dfmi::UwState), (void**)&tiles))) return rc;
+    if ((rc = workspace("uw_lead", (size_t)nser * 8, (void**)&lead))) return rc;
+  }
+  HIPCHK(dfmi::unwrap_launch(dx, nser, xs, N, period, dstat, ss, max_status, fill, dy, dys, dc, dcs, path, tiles, lead, st));
+  if (sg.host && y)
+    HIPCHK(hipMemcpy2DAsync(y, (size_t)ys * 8, dy, (size_t)dys * 8, (size_t)N * 8, (size_t)nser, hipMemcpyDeviceToHost, st));
+  if (sg.host && cycles)
+    HIPCHK(hipMemcpy2DAsync(cycles, (size_t)cys * 8, dc, (size_t)dcs * 8, (size_t)N * 8, (size_t)nser,
                             hipMemcpyDeviceToHost, st));
   return sg.finish();
 }

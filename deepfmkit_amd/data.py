@@ -98,6 +98,15 @@ class DeepFitObject:
         return dict(olap=self.olap, bmin=self.bmin, Lmin=self.Lmin, Jdes=self.Jdes, Kdes=self.Kdes, order=self.order,
                     win=self.win, psll=self.psll)
 
+    def unwrap(self, which="phi"):
+        """Unwraps the fitted `which` by 2 pi on the GPU (deepfmkit_amd.series.unwrap), stepping
+        over non-finite values only (a fit loaded from text carries no fitok): sets and returns
+        `<which>_unwrapped`, which calc_lpsd(which="phi_unwrapped") then reads."""
+        from .series import unwrap
+        y = unwrap(np.asarray(getattr(self, which), dtype=np.float64))
+        setattr(self, which + "_unwrapped", y)
+        return y
+
     def calc_lpsd(self, which="phi"):
         """LPSD of a fitted parameter (the reference's calc_lpsd takes phi, data.py:239-244) at
         the fit data rate fs with this object's settings: sets f and Sxx, on the GPU

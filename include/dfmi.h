@@ -38,6 +38,7 @@
  *   dfmi_wdfmi_fit   WDFMI_NLSFitter / WDFMI_OrthogonalFitter / WDFMI_SequentialFitter /
  *                    HWDFMI_Fitter .fit (fitters.py:481-891)
  *   dfmi_residual    the time-domain residual of the fitted model per segment: rss, peak, the record
+ *   dfmi_unwrap      no counterpart: fit.fit leaves phi wrapped to (-pi, pi] (fit.py:359-360)
  *   dfmi_fisher      the J^T J of coeffs (fit.py:68-150) and its inverse at caller points:
  *                    calculate_crlb_for_m / calculate_m_precision (helpers.py:16-45, 98-132),
  *                    and the per-segment standard errors of a fit (no reference counterpart)
@@ -560,6 +561,49 @@ int dfmi_lcsd(const double* x, int64_t x_stride, const double* y, int64_t y_stri
               double* Sxx, double* Syy, double* Sxy_re, double* Sxy_im, double* coh, double* enbw,
               int32_t mem, void* stream);
 
+/* ---- Phase unwrapping of fitted series, bridging failed fits ----
+ * dfmi_unwrap: removes the jumps of a multiple of `period` from nser series of N float64
+ * samples as an exact integer scan. The reference leaves phi wrapped to
+ * (-pi, pi] (fit.py:359-360).
+ * Series and validity:
+ *   series r is x[r*ser_stride + i], i < N.
+ *   Point i is valid when x is finite and, if status != NULL,
+ *   0 <= status[r*status_stride + i] <= max_status.
+ *   This reads dfmi_nls_record's out + 2*ld (phi) and fitok in place, with
+ *   ser_stride = status_stride = nbuf.
+ * Cycle counts:
+ *   let v0 < v1 < ... be the valid points of a series, and P = period.
+ *   c[v0] = 0.
+ *   c[v_j] = c[v_{j-1}] - rint(d / P), with d = x[v_j] - x[v_{j-1}].
+ *   All of it is in double: one rounded subtraction, one rounded division, round-half-to-even.
+ *   Counts are int64 throughout, because period is free and |rint| is not bounded by 1.
+ * Output at valid points:
+ *   y[v] = fma((double)c[v], P, x[v]), with a single rounding, and cycles[v] = c[v].
+ *   So y - x is an exact cycle count times P, consecutive valid points differ by at most P/2,
+ *   and the result does not depend on the launch geometry or the batch.
+ * Output at invalid points (gaps):
+ *   fill == 0: y = NaN.
+ *   fill == 1: y holds the previous valid point's y, or the first valid point's y before any
+ *   valid point.
+ *   cycles at a gap is the count held the same way.
+ *   A series with no valid point is all NaN with cycles 0.
+ * Optional outputs: y (at y[r*y_stride + i]) or cycles (at cycles[r*cycles_stride + i]) may be
+ * NULL, but not both.
+ * DFMI_ERR_ARG, before any device work: a non-finite or non-positive period; nser < 0, or N < 0
+ * or N >= 2^31; strides smaller than N when nser > 1; fill outside 0..1; y == x, since in-place
+ * is not supported.
+ * Empty input: nser == 0 or N == 0 launches nothing.
+ * Host memory: DFMI_MEM_HOST stages the data as dfmi_lpsd does (the caller's memory between the
+ * rows of y and cycles is not written). On DFMI_MEM_DEVICE the kernels are enqueued on `stream`
+ * and not waited for. Any alignment; rows of x, y and cycles on 16-byte boundaries are read and
+ * written 16 bytes per lane. Two geometries give the same bits (tuning key "unwrap_path"): one
+ * workgroup per series, or, for a few long series, three launches over tiles of 1,024 points
+ * whose 32-byte states live in the library's workspaces (dfmi_release_workspaces). */
+int dfmi_unwrap(const double* x, int64_t nser, int64_t ser_stride, int64_t N, double period,
+                const int32_t* status, int64_t status_stride, int32_t max_status, int32_t fill,
+                double* y, int64_t y_stride, int64_t* cycles, int64_t cycles_stride,
+                int32_t mem, void* stream);
+
 /* ---- Witness-based fitters (EXPERIMENTAL in the reference) ----
  * Replace, per record (main channel + witness channel):
  *   DFMI_WDFMI_NLS    WDFMI_NLSFitter.fit        fitters.py:481-570 (least_squares(method='lm'))
@@ -658,7 +702,9 @@ int dfmi_wdfmi_fit(const double* x, int64_t nrec, int64_t rec_stride, int64_t nb
  * many items per CU, default 4: one wave per item as 8 rungs x 8 harmonic shares; 0 = 8 lanes
  * per item; rounding only), "lpsd_batch_mb" (dfmi_lpsd: MiB of window and per-segment workspace
  * per batch of frequencies, default 512; a batch holds at least one frequency, 0 = one frequency
- * per batch; same bits),
+ * per batch; same bits), "unwrap_path" (dfmi_unwrap: 0 [default] the series kernel from two
+ * series per CU or for a single tile and the tiled path below that, 1 the series kernel, 2 the
+ * tiled path; same bits),
  * "probe" (1 =
  * diagnostics timestamp buffer on the current device, dfmi_probe_read). */
 int dfmi_set_tuning(const char* key, int64_t value);
